@@ -77,7 +77,14 @@ def parse():
     ap.add_argument("--pipeline", action="store_true",
                     help="alternate two contexts between consecutive steps (independent batches overlap; "
                          "per-kernel durations then overlap too, so the default keeps one context)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy in float64: "
+                         "the arrays a caller of the step's path receives (see dump_outputs); at most 64 MB in all, a fixed "
+                         "seeded sample of rows where an output is larger; an empty output is not written")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_batch(args, rank):
@@ -352,6 +359,81 @@ class ResidentCollect:
         for x in list(self.d.values()) + self.o + [self.d_segs, self.d_rl, self.d_raw, self.d_post, self.d_cnt] + \
                 ([self.d_deal] if self.d_deal else []):
             x.free()
+
+
+# ---- --dump-outputs: what the timed path computed in its last step, for output-by-output comparison of two builds
+SIG_KEYS = ("aln", "ref_pos", "read_pos", "len", "type")
+RAW_WORDS = 7  # kind, a0..a5 of an svx_raw / svx_post record; the eighth word is padding
+# rows kept per output group, sampled row numbers included (float64, 8 B a value):
+# (5 + 1) x 600 k + 2 x (7 + 1) x 200 k + 2 x 200 k values, 57.6 MB at most
+DUMP_ROW_CAP = {"sig": 600_000, "raw": 200_000, "post": 200_000, "post_first": 200_000}
+DUMP_MAX_BYTES = 64 << 20
+
+
+def collect_outputs(rc):
+    """What svx_collect_batch hands its caller (Context.collect_batch): the indel signatures, the decision tree's raw
+    record per segment, the derived records packed read by read and the first of them per read."""
+    rc.ctx.sync()
+    case = rc.case
+    k = rc.n_sig()
+    if k > rc.cap:
+        raise SystemExit("output capacity too small: %d > %d" % (k, rc.cap))
+    out = {"sig_" + key: x.download(np.uint8 if key == "type" else np.uint32, k) for x, key in zip(rc.o[:5], SIG_KEYS)}
+    out["n_sig"] = np.array([k])
+    out["raw"] = rc.d_raw.download(np.int32, 8 * case["n_segs"]).reshape(-1, 8)[:, :RAW_WORDS]
+    post_off = case["post_off"].astype(np.int64)
+    slots = rc.d_post.download(np.int32, 8 * int(post_off[-1])).reshape(-1, 8)[:, :RAW_WORDS]
+    cnt = rc.d_cnt.download(np.uint32, case["n_reads"]).astype(np.int64)
+    first = np.concatenate(([0], np.cumsum(cnt)))
+    out["post"] = slots[np.repeat(post_off[:-1] - first[:-1], cnt) + np.arange(int(first[-1]))]
+    out["post_first"] = first
+    return out
+
+
+def split_outputs(o, d_raw, cap):
+    """--step split: what svx_cigar_extract and svx_segments_classify hand their callers (the signatures; the raw
+    record per segment)."""
+    k = int(o[5].item())
+    if k > cap:
+        raise SystemExit("output capacity too small: %d > %d" % (k, cap))
+    out = {"sig_" + key: t[:k].cpu().numpy() for t, key in zip(o[:5], SIG_KEYS)}
+    out = {name: a.view(np.uint32) if a.dtype == np.int32 else a for name, a in out.items()}
+    out["n_sig"] = np.array([k])
+    out["raw"] = d_raw.cpu().numpy()[:, :RAW_WORDS]
+    return out
+
+
+def dump_outputs(dirname, out):
+    """Every output as DIR/<name>.npy in float64 (exact for the u8 / i32 / u32 fields).  An output group longer than
+    its row cap keeps a fixed, seeded sample of rows, the same for every member of the group (the five signature
+    columns share theirs), and the sampled row numbers go beside it as DIR/<group>_rows.npy.  An output with no
+    elements (the derived records of a workload whose reads yield none) is not written — there is nothing in it to
+    compare — and is named on stderr instead."""
+    rows, arrays = {}, {}
+    empty = [name for name, a in out.items() if np.size(a) == 0]
+    for name, a in out.items():
+        if name in empty:
+            continue
+        group = "sig" if name.startswith("sig_") else name
+        cap = DUMP_ROW_CAP.get(group)
+        if cap is not None and len(a) > cap:
+            if group not in rows:
+                rows[group] = np.sort(np.random.default_rng(0).choice(len(a), size=cap, replace=False))
+                arrays[group + "_rows"] = rows[group].astype(np.float64)
+            a = a[rows[group]]
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    # files of this dump's own names that an earlier dump into DIR left and this one does not write
+    for name in empty + [g + "_rows" for g in DUMP_ROW_CAP if g + "_rows" not in arrays]:
+        if os.path.exists(os.path.join(dirname, name + ".npy")):
+            os.remove(os.path.join(dirname, name + ".npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print("bench.py: wrote %d outputs of the last timed step (%.1f MB) to %s%s" % (
+        len(arrays), total / 1e6, dirname, "; empty, not written: " + ", ".join(empty) if empty else ""), file=sys.stderr)
 
 
 def collect_leg(args, local_rank, torch, batches, what, seed):
@@ -951,6 +1033,10 @@ def main():
     thr1 = _throttled_us()
     host_throttled_ms = None if thr0 is None or thr1 is None else (thr1 - thr0) / 1e3
     own_elapsed = elapsed
+    if args.dump_outputs and rank == 0:  # (later regions, the timing and the check below overwrite these buffers)
+        last = (step_no[0] - 1) % len(ctxs)
+        dump_outputs(args.dump_outputs, collect_outputs(rcs[last]) if args.step == "collect" else
+                     split_outputs(out_sets[last], d_raw, cap))
     # `value` is the region above — the FIRST `steps` steps behind the warm-up, as the contract asks.  Four more regions of
     # the same length, bracketed the same way, give the spread of a 7-ms measurement (`value_median_of_5`).
     repeats = [elapsed]

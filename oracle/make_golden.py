@@ -16,7 +16,9 @@ replaced by an exact Levenshtein DP).  What is captured:
   * tests/golden/pipeline_vectors.json.gz   function-level vectors of the callers either side of the
     kernels: analyze_alignment_file_coordsorted (COLLECT), analyze_read_segments per read,
     form_partitions, pair_candidates — inputs as plain records / candidate tuples, outputs as the
-    canonical candidate tuples of the REAL reference's objects.
+    canonical candidate tuples of the REAL reference's objects;
+  * tests/golden/reference_diff.json.gz   the reference's answers to the seeded cases of the randomised
+    differential tests (tests/test_oracle_vs_reference.py, tests/test_product_vs_reference_cpu.py).
 """
 import importlib.machinery
 import importlib.util
@@ -562,6 +564,53 @@ def make_pipeline_vectors():
         fh.write(json.dumps(vec).encode())  # (mtime 0: regenerating the fixture leaves the bytes unchanged)
 
 
+def make_reference_diff():
+    """What the real reference returns for the seeded cases of tests/test_oracle_vs_reference.py and
+    tests/test_product_vs_reference_cpu.py: COLLECT / pair_candidates as canonical candidate tuples and the VCF text
+    of write_final_vcf (##fileDate masked).  The inputs are not stored (they come from the seeded generators of
+    tests/helpers.py), only their digest, which the tests check."""
+    import gzip
+    ref = load_reference()
+    from tests import helpers
+    from tests import test_oracle_vs_reference as t_orc
+    from tests import test_product_vs_reference_cpu as t_prod
+    names, lengths = t_orc.NAMES, t_orc.LENGTHS
+
+    def collect(recs, o):
+        digest = helpers.inputs_digest(recs, o)
+        out = [helpers.candidate_tuple(c) for c in
+               ref["COLLECT"].analyze_alignment_file_coordsorted(_ref_stub_bam(recs, names, lengths), o)]
+        return {"inputs_sha256": digest, "out": out}
+
+    def pair(seqs, lens, t1, t2, o):
+        digest = helpers.inputs_digest((seqs, t1, t2), o)
+
+        class Bam(object):
+            references = tuple(names)
+
+            def get_reference_length(self, n):
+                return lens[names.index(n)]
+        fasta = helpers.FakeFasta(seqs)
+        objs = ref["COMBINE"].pair_candidates([helpers.build_candidate(t, Bam(), ref["CAND"]) for t in t1],
+                                              [helpers.build_candidate(t, Bam(), ref["CAND"]) for t in t2], fasta, Bam(), o)
+        wd = tempfile.mkdtemp(prefix="svx_refdiff_")
+        o.working_dir = wd
+        by = lambda t: [c for c in objs if c.type == t]
+        ref["COMBINE"].write_final_vcf(by("DUP_INT"), by("INV"), by("DUP_TAN"), by("DEL"), by("INS"), by("BND"), "1.0.3",
+                                       names, lens, [t.strip() for t in o.types.split(",")], helpers.FakeFasta(seqs), o)
+        vcf = masked_vcf(os.path.join(wd, "variants.vcf"))
+        shutil.rmtree(wd)
+        return {"inputs_sha256": digest, "out": [helpers.candidate_tuple(c) for c in objs], "vcf": vcf}
+
+    vec = {"oracle": {"collect": [collect(*t_orc.collect_case(s)) for s in range(8)],
+                      "all_types": collect(*t_orc.all_types_case()),
+                      "pair": [pair(*t_orc.pair_case(s)) for s in range(6)]},
+           "product": {"collect": [collect(*t_prod.collect_case(s)) for s in range(6)],
+                       "pair": [pair(*t_prod.pair_case(s)) for s in range(4)]}}
+    with gzip.GzipFile(os.path.join(GOLD, "reference_diff.json.gz"), "wb", compresslevel=9, mtime=0) as fh:
+        fh.write(json.dumps(vec).encode())
+
+
 def main():
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
@@ -571,11 +620,12 @@ def main():
         for what in sys.argv[1:]:
             {"functions": make_function_vectors, "config1": make_config1, "medium": make_medium,
              "longcigar": make_longcigar, "pipeline": make_pipeline_vectors, "large": make_large, "full": make_full, "config5": make_config5, "medium_options": make_medium_options,
-             "digests": refresh_payload_digests}[what]()
+             "digests": refresh_payload_digests, "refdiff": make_reference_diff}[what]()
         return
     make_longcigar()
     make_function_vectors()
     make_pipeline_vectors()
+    make_reference_diff()
     out = make_config1()
     make_medium()
     # the two reference BAM fixtures are data, not source: keep copies for the GPU box

@@ -363,6 +363,33 @@ def load_pipeline_vectors():
     return vec
 
 
+# ---- reference answers of the randomised differential tests (tests/golden/reference_diff.json.gz) ---------
+def inputs_digest(inputs, o):
+    """sha256 of a differential case's inputs and options, as the real reference was given them."""
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps([inputs, vars(o)], sort_keys=True).encode()).hexdigest()
+
+
+def load_reference_diff():
+    """What the real reference returned for the cases of tests/test_oracle_vs_reference.py and
+    tests/test_product_vs_reference_cpu.py (oracle/make_golden.py refdiff)."""
+    import gzip
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_diff.json.gz")
+    with gzip.open(path, "rt") as fh:
+        return json.load(fh)
+
+
+def reference_answer(entry, inputs, o):
+    """The stored candidate tuples of one case, after checking that the seeded generators still make the inputs the
+    reference was run on.  A difference is a failure, never a skip."""
+    assert inputs_digest(inputs, o) == entry["inputs_sha256"], \
+        "regenerated inputs differ from those the reference answered (generator drift)"
+    return [_tuplify(t) for t in entry["out"]]
+
+
 # ---- the device replaced by the oracle (CPU-side tests of the host logic) -------------------------
 class OracleBackedContext(object):
     """Stands in for svim_asm_amd._svxlib().Context with every device entry point answered by the CPU oracle, so
