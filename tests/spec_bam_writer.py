@@ -75,14 +75,15 @@ def encode_record(r, long_cigar_as_tag=True):
     return struct.pack("<i", len(body)) + body
 
 
-def bgzf_member(payload, level=6):
-    """One BGZF block (§4.1): gzip member with the BC extra field; payload at most 65280 bytes here."""
+def bgzf_member(payload, level=6, compress=None):
+    """One BGZF block (§4.1): gzip member with the BC extra field; payload at most 65280 bytes here.  `compress`: a
+    callable that makes the raw DEFLATE stream of the payload in place of zlib at `level` (tests/deflate_writer.py)."""
     assert len(payload) <= 65536
-    if level == 0:
-        comp = zlib.compressobj(0, zlib.DEFLATED, -15)
+    if compress is not None:
+        cdata = compress(payload)
     else:
         comp = zlib.compressobj(level, zlib.DEFLATED, -15)
-    cdata = comp.compress(payload) + comp.flush()
+        cdata = comp.compress(payload) + comp.flush()
     bsize = 12 + 6 + len(cdata) + 8
     assert bsize <= 65536
     head = struct.pack("<BBBBIBBH", 0x1F, 0x8B, 8, 4, 0, 0, 0xFF, 6) + b"BC" + struct.pack("<HH", 2, bsize - 1)
@@ -93,11 +94,11 @@ EOF_MARKER = bytes.fromhex("1f8b08040000000000ff0600424302001b000300000000000000
 
 
 def write_bam(path, refs, records, header_text=None, cuts=None, chunk=65280, level=6, empty_after=(), index=True,
-              pseudo_bins=True, n_no_coor=True, extra_subfield=False):
+              pseudo_bins=True, n_no_coor=True, extra_subfield=False, compress=None):
     """refs: [(name, length)]; records in file order.  The uncompressed stream is cut into members at the byte
     positions `cuts` (absolute offsets into the stream) or every `chunk` bytes; after member number k in
-    `empty_after` an EMPTY member (ISIZE 0) is inserted.  Returns the virtual offset (coffset << 16 | uoffset) of
-    every record's start and end."""
+    `empty_after` an EMPTY member (ISIZE 0) is inserted; `compress` as in bgzf_member.  Returns the virtual offset
+    (coffset << 16 | uoffset) of every record's start and end."""
     if header_text is None:
         header_text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, l) for n, l in refs)
     text = header_text.encode()
@@ -118,10 +119,10 @@ def write_bam(path, refs, records, header_text=None, cuts=None, chunk=65280, lev
     for a, b in zip(bounds, bounds[1:]):
         while b - a > 65280:
             member_at.append((a, a + 65280, len(out)))
-            out += bgzf_member(bytes(stream[a:a + 65280]), level)
+            out += bgzf_member(bytes(stream[a:a + 65280]), level, compress)
             a += 65280
         member_at.append((a, b, len(out)))
-        m = bgzf_member(bytes(stream[a:b]), level)
+        m = bgzf_member(bytes(stream[a:b]), level, compress)
         if extra_subfield:  # another extra subfield in front of BC: readers must walk the subfields
             cdata = m[18:]
             bsize = 12 + 6 + 6 + len(cdata)
@@ -129,7 +130,7 @@ def write_bam(path, refs, records, header_text=None, cuts=None, chunk=65280, lev
                 struct.pack("<HH", 2, bsize - 1) + cdata
         out += m
         if k in empty_after:
-            out += bgzf_member(b"", level)
+            out += bgzf_member(b"", level, compress)
         k += 1
     out += EOF_MARKER
     with open(path, "wb") as fh:
