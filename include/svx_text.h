@@ -39,6 +39,34 @@ void svx_fasta_close(svx_fasta* fa);
 int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end,
                           uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads);
 
+/*
+ * A bgzip-compressed FASTA (htslib faidx semantics): the .fai columns count UNCOMPRESSED bytes, and
+ * gzi_coff / gzi_uoff[n_gzi] are the `<path>.gzi` pairs (compressed offset of a member, uncompressed offset of its
+ * first byte; (0, 0) implicit, a final entry at the end of the data allowed).  At open the whole member chain is
+ * walked (header, BSIZE, ISIZE): every .gzi entry must lie on a member header with the uncompressed offset the chain
+ * gives, the offsets must increase, and the chain must end exactly at the end of the file.  svx_fasta_fetch_batch
+ * then inflates every member under its windows once (the build's own decoder, CRC32 and ISIZE checked as htslib's
+ * BGZF reader does) on the handle's threads, or on the device (svx_fasta_set_device), and gathers the bases as for a
+ * plain file.  A damaged member under a window: SVX_E_INVALID, svx_fasta_last_error names its compressed offset.
+ */
+int svx_fasta_open_bgzf(const char* path, int32_t n_refs, const int64_t* length, const int64_t* offset,
+                        const int32_t* line_bases, const int32_t* line_width, const uint64_t* gzi_coff,
+                        const uint64_t* gzi_uoff, uint64_t n_gzi, svx_fasta** out, char* err, size_t err_cap);
+/* 1 for a handle of svx_fasta_open_bgzf, 0 otherwise */
+int svx_fasta_is_bgzf(const svx_fasta* fa);
+/* device >= 0: batch calls that touch at least min_members distinct members inflate the members that are not resident
+ * yet on that device (svx_bgzf_inflate_on_stream) and gather the windows there; the inflated members stay resident
+ * (up to 6 GiB) until svx_fasta_close.  device < 0: host threads only (the default).  Where no device can be brought
+ * up the call runs on the host threads and writes the same bytes.  No effect on a plain file. */
+int svx_fasta_set_device(svx_fasta* fa, int device, uint32_t min_members);
+/* counters of a compressed handle (all 0 for a plain one): out[SVX_FASTA_STATS] = members inflated on the host, on
+ * the device, compressed bytes staged for the device, member look-ups served from the host cache or the device arena,
+ * device calls, host calls */
+#define SVX_FASTA_STATS 6
+int svx_fasta_stats(const svx_fasta* fa, uint64_t* out);
+/* the last error of a failed fetch ("" when none) */
+const char* svx_fasta_last_error(const svx_fasta* fa);
+
 /* -------------------------------------------------------------------- VCF ---- */
 /*
  * The record lines of write_final_vcf (SVIM_COMBINE.py:428-477): one call formats every entry, sorts them the

@@ -203,6 +203,12 @@ SYMBOLS = {
     "svx_fasta_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, _P, _P, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_fasta_close": (None, [_P]),
     "svx_fasta_fetch_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_int]),
+    "svx_fasta_open_bgzf": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(_P), C.c_char_p,
+                                      C.c_size_t]),
+    "svx_fasta_is_bgzf": (C.c_int, [_P]),
+    "svx_fasta_set_device": (C.c_int, [_P, C.c_int, C.c_uint32]),
+    "svx_fasta_stats": (C.c_int, [_P, _P]),
+    "svx_fasta_last_error": (C.c_char_p, [_P]),
     "svx_vcf_format": (C.c_int, [C.POINTER(VcfIn), C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "svx_vcf_free": (None, [_P]),
     "svx_vcf_write": (C.c_int, [C.POINTER(VcfIn), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -7,7 +7,7 @@ import sys
 from time import localtime, strftime
 
 from svim_asm_amd import _timeline, bamio, shard
-from svim_asm_amd.fasta import FastaFile
+from svim_asm_amd.fasta import BgzfFormatError, FastaFile, MissingGziError
 from svim_asm_amd.SVIM_COMBINE import write_vcf_table
 from svim_asm_amd.table import TYPE_ORDER
 from svim_asm_amd.SVIM_input_parsing import parse_arguments
@@ -214,7 +214,14 @@ def _run_steps(options):
             _timeline.mark("COLLECT done", stages=dict(SVIM_COLLECT.LAST_TIMING))
 
     try:
-        reference = FastaFile(options.genome)
+        reference = FastaFile(options.genome, device=getattr(options, "device", None))
+    except MissingGziError:
+        logging.error("The given reference genome is bgzip-compressed and is missing its index file ({0}.gzi). Sequence "
+                      "alleles cannot be retrieved.".format(options.genome))
+        return
+    except BgzfFormatError as e:
+        logging.error("The given reference genome cannot be read ({0}). Sequence alleles cannot be retrieved.".format(e))
+        return
     except ValueError:
         logging.error("The given reference genome is missing an index file ({0}.fai). Sequence alleles cannot be "
                       "retrieved.".format(options.genome))

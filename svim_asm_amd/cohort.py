@@ -22,7 +22,7 @@ import os
 import sys
 
 from svim_asm_amd import SVIM_COLLECT, _timeline, cli, shard
-from svim_asm_amd.fasta import FastaFile
+from svim_asm_amd.fasta import BgzfFormatError, FastaFile, MissingGziError
 from svim_asm_amd.SVIM_COMBINE import write_vcf_table
 from svim_asm_amd.SVIM_input_parsing import parse_arguments
 
@@ -161,7 +161,15 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
     tables = SVIM_COLLECT.collect_tables(files, group[0][0], ctx=ctx)
     _timeline.mark("COLLECT done", sample=first_no)
     for k, (o, wd, bams) in enumerate(group):
-        reference = FastaFile(genome)  # (write_final_vcf closes its FastaFile, SVIM_COMBINE.py:466-467: one per sample)
+        try:  # (write_final_vcf closes its FastaFile, SVIM_COMBINE.py:466-467: one per sample)
+            reference = FastaFile(genome, device=getattr(o, "device", 0) or 0)
+        except MissingGziError:
+            logging.error("The given reference genome is bgzip-compressed and is missing its index file ({0}.gzi). Sequence "
+                          "alleles cannot be retrieved.".format(genome))
+            return 1
+        except BgzfFormatError as e:
+            logging.error("The given reference genome cannot be read ({0}). Sequence alleles cannot be retrieved.".format(e))
+            return 1
         mine, mine_files = tables[k * n_bams:(k + 1) * n_bams], files[k * n_bams:(k + 1) * n_bams]
         candidates = pair_tables(mine[0], mine[1], reference, mine_files[0], o, ctx=ctx) if mode == "diploid" else mine[0]
         # as cli._run_steps: a damaged BGZF member among the inserted-sequence bytes must fail the run before a VCF is

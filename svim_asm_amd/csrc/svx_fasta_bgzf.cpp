@@ -1,0 +1,673 @@
+// svx_fasta_bgzf.cpp — the bgzip-compressed form of the FASTA handle (svx_fasta_open_bgzf, include/svx_text.h), host C++.
+//
+// What htslib's faidx does with `ref.fa.gz` + `.fai` + `.gzi` (BGZF: SAM specification §4.1; the .gzi layout: a
+// little-endian uint64 count, then (compressed, uncompressed) uint64 pairs, (0, 0) implicit).  The .fai offsets count
+// uncompressed bytes; a window [start, end) of a sequence is the byte range fetch_one of svx_text.cpp reads, and the
+// members under it are found by the uncompressed offsets of the member chain.
+//
+// Host path: the distinct members under a batch's windows are inflated once each (svx_inflate_raw_pair, two side by side)
+// on up to 16 threads, CRC32 and ISIZE checked; then the windows are gathered from the inflated members.  Batches are cut
+// into groups of at most kGroupMembers distinct members (in order of the windows' first member) so that a genome-wide call
+// never holds more than that many inflated members at once.  A few recent members stay cached for the short fetches that
+// follow each other (fetch() of the VCF's alleles).
+//
+// Device path (svx_fasta_set_device): the members not yet resident are staged through page-locked memory, inflated and
+// checked by svx_inflate.hip's kernels into an arena that stays on the device for the handle's life, and the windows are
+// gathered there by svx_fasta_gather.hip; the packed bytes come back to the caller's buffer.  Any failure to bring the
+// device up sends the call to the host path (same bytes); a member the device finds damaged fails the call as on the host.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <atomic>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "svx.h"
+#include "svx_bam.h"
+#include "svx_fasta_bgzf.h"
+#include "svx_inflate_dev.h"
+#include "svx_text.h"
+
+namespace {
+
+inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
+inline uint32_t le32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+constexpr uint32_t kGroupMembers = 4096;   // inflated members a host call holds at once (256 MiB)
+constexpr size_t kCacheMembers = 8;        // recent members kept between calls
+constexpr uint64_t kArenaCap = 6ull << 30;  // device-resident inflated members of one handle
+
+svx_inflate_launch_fn g_inflate = nullptr;   // svx_fasta_gather.hip registers the launches when the library loads
+svx_fasta_gather_fn g_gather = nullptr;
+svx_inflate_arena_fn g_arena = nullptr;
+
+bool host_only_env() {
+    static const bool off = [] { const char* e = getenv("SVX_FASTA_DEVICE"); return e && e[0] == '0'; }();
+    return off;
+}
+
+struct Member {
+    uint64_t coff, uoff;
+    uint32_t payload_off, payload_len, isize, crc;
+};
+
+// one member's header at coff: 0 ok, -1 malformed (BGZF: gzip magic, CM 8, FLG.FEXTRA, a BC subfield of length 2)
+int parse_member(const uint8_t* map, uint64_t fsize, uint64_t coff, Member* m, uint32_t* bsize) {
+    if (coff + 18 > fsize) return -1;
+    const uint8_t* p = map + coff;
+    if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || !(p[3] & 4)) return -1;
+    const uint32_t xlen = le16(p + 10);
+    if (coff + 12 + xlen > fsize) return -1;
+    uint32_t q = 12, end = 12 + xlen, bs = 0;
+    while (q + 4 <= end) {
+        const uint32_t slen = le16(p + q + 2);
+        if (p[q] == 66 && p[q + 1] == 67 && slen == 2 && q + 6 <= end) bs = (uint32_t)le16(p + q + 4) + 1;
+        q += 4 + slen;
+    }
+    if (!bs || bs < xlen + 20 || coff + bs > fsize) return -1;
+    m->coff = coff;
+    m->payload_off = 12 + xlen;
+    m->payload_len = bs - xlen - 20;
+    m->crc = le32(p + bs - 8);
+    m->isize = le32(p + bs - 4);
+    if (m->isize > 65536) return -1;
+    *bsize = bs;
+    return 0;
+}
+
+using Buf = std::shared_ptr<std::vector<uint8_t>>;
+
+struct Fz {
+    const uint8_t* map = nullptr;
+    uint64_t fsize = 0, total = 0;
+    std::vector<Member> mem;        // the chain, in file order
+    std::vector<uint64_t> uoff;     // mem[i].uoff, for the searches
+    mutable std::mutex mu;          // everything below
+    std::string err;
+    std::vector<std::pair<uint32_t, Buf>> cache;  // most recent last
+    uint64_t stat[SVX_FASTA_STATS] = {0, 0, 0, 0, 0, 0};
+    // device
+    int device = -1;
+    uint32_t dev_min = 64;
+    bool dev_broken = false;
+    hipStream_t stream = nullptr;
+    uint8_t* d_arena = nullptr;   // resident members
+    uint64_t arena_cap = 0, arena_used = 0;
+    std::vector<uint64_t> slot;   // arena offset of member i, ~0: not resident
+    uint8_t* d_scratch = nullptr;  // a call's payloads, tables, token lists and packed output
+    uint64_t scratch_cap = 0;
+    uint8_t* h_stage = nullptr;    // page-locked staging
+    uint64_t stage_cap = 0;
+
+    // the member that holds uncompressed byte u (u < total): the last one starting at or before u (empty members
+    // start where the next one does, so they are never it)
+    uint32_t member_of(uint64_t u) const {
+        return (uint32_t)(std::upper_bound(uoff.begin(), uoff.end(), u) - uoff.begin() - 1);
+    }
+    uint32_t next_nonempty(uint32_t m) const {
+        uint32_t k = m + 1;
+        while (k < mem.size() && mem[k].isize == 0) ++k;
+        return k;
+    }
+    void set_err(const std::string& s) {
+        std::lock_guard<std::mutex> g(mu);
+        err = s;
+    }
+    void free_device() {
+        if (device < 0 || (!stream && !d_arena && !d_scratch && !h_stage)) return;  // (nothing was brought up: no runtime call)
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (d_arena) (void)hipFree(d_arena);
+        if (d_scratch) (void)hipFree(d_scratch);
+        if (h_stage) (void)hipHostFree(h_stage);
+        if (stream) (void)hipStreamDestroy(stream);
+        (void)hipGetLastError();
+        d_arena = d_scratch = h_stage = nullptr;
+        stream = nullptr;
+        arena_cap = arena_used = scratch_cap = stage_cap = 0;
+        slot.assign(mem.size(), ~0ull);
+    }
+};
+
+std::string member_msg(const char* what, uint64_t coff) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s BGZF member at compressed offset %llu", what, (unsigned long long)coff);
+    return buf;
+}
+
+// member m inflated whole into out[isize]: its CRC32 and ISIZE checked
+bool inflate_member(const Fz* z, uint32_t m, uint8_t* out) {
+    const Member& M = z->mem[m];
+    uint64_t n_out = 0;
+    if (svx_inflate_raw(z->map + M.coff + M.payload_off, M.payload_len, out, M.isize, nullptr, 0, &n_out) != SVX_OK) return false;
+    return n_out == M.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), out, M.isize) == M.crc;
+}
+void inflate_two(const Fz* z, uint32_t ma, uint8_t* oa, uint32_t mb, uint8_t* ob, bool* ok_a, bool* ok_b) {
+    const Member &A = z->mem[ma], &B = z->mem[mb];
+    uint64_t na = 0, nb = 0;
+    int ra = SVX_E_INVALID, rb = SVX_E_INVALID;
+    if (svx_inflate_raw_pair(z->map + A.coff + A.payload_off, A.payload_len, oa, A.isize, ~0ull, &na, &ra,
+                             z->map + B.coff + B.payload_off, B.payload_len, ob, B.isize, ~0ull, &nb, &rb) != SVX_OK) {
+        *ok_a = inflate_member(z, ma, oa);  // (the pair call refused its arguments: each on its own, so that the
+        *ok_b = inflate_member(z, mb, ob);  //  damaged one is the one named)
+        return;
+    }
+    *ok_a = ra == SVX_OK && na == A.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), oa, A.isize) == A.crc;
+    *ok_b = rb == SVX_OK && nb == B.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), ob, B.isize) == B.crc;
+}
+
+// the uncompressed byte range of bases [s, e) of sequence r (as fetch_one of svx_text.cpp computes it)
+inline void byte_range(const svx_fasta_geom* g, int32_t r, int64_t s, int64_t e, uint64_t* b0, uint64_t* b1) {
+    const int64_t lb = g->line_bases[r], lw = g->line_width[r], off = g->offset[r];
+    *b0 = (uint64_t)(off + (s / lb) * lw + s % lb);
+    *b1 = (uint64_t)(off + ((e - 1) / lb) * lw + (e - 1) % lb + 1);
+}
+
+inline uint8_t ascii_upper(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
+
+// bases of [s, e) from raw bytes [b0, b1) into dst: line ends skipped, upper-cased when asked (fetch_one's loop)
+void lines_to_bases(const svx_fasta_geom* g, int32_t r, int64_t s, int64_t e, bool upper, uint8_t* raw, size_t n, uint8_t* dst) {
+    const int64_t lb = g->line_bases[r], lw = g->line_width[r];
+    if (upper)
+        for (size_t i = 0; i < n; ++i) raw[i] = ascii_upper(raw[i]);
+    const uint8_t* src = raw;
+    int64_t left = e - s;
+    int64_t take = std::min<int64_t>(lb - s % lb, left);
+    for (;;) {
+        memcpy(dst, src, (size_t)take);
+        dst += take;
+        left -= take;
+        if (left <= 0) break;
+        src += take + (lw - lb);
+        take = std::min<int64_t>(lb, left);
+    }
+}
+
+int run_threads(int n_threads, const std::function<void()>& fn) {
+    if (n_threads <= 1) {
+        fn();
+        return SVX_OK;
+    }
+    try {
+        std::vector<std::thread> th;
+        for (int t = 0; t < n_threads; ++t) th.emplace_back(fn);
+        for (std::thread& t : th) t.join();
+    } catch (...) {
+        return SVX_E_NOMEM;
+    }
+    return SVX_OK;
+}
+
+// ------------------------------------------------------------------ open / close
+int z_open(const uint8_t* map, uint64_t size, const uint64_t* gzi_coff, const uint64_t* gzi_uoff, uint64_t n_gzi, void** out,
+           char* err, size_t err_cap) {
+    auto fail = [&](const std::string& s) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", s.c_str());
+        return SVX_E_INVALID;
+    };
+    std::unique_ptr<Fz> z(new (std::nothrow) Fz());
+    if (!z) return SVX_E_NOMEM;
+    z->map = map;
+    z->fsize = size;
+    // the .gzi behind the implicit (0, 0) (an explicit one in front is tolerated): compressed offsets strictly increasing,
+    // uncompressed ones not decreasing — an empty member in the middle (bgzip files concatenated, each with its end-of-file
+    // marker) starts where the next member does; the walk below checks every entry against the members' ISIZE
+    uint64_t g0 = (n_gzi && gzi_coff[0] == 0 && gzi_uoff[0] == 0) ? 1 : 0;
+    for (uint64_t i = g0; i < n_gzi; ++i) {
+        const uint64_t pc = i > g0 ? gzi_coff[i - 1] : 0, pu = i > g0 ? gzi_uoff[i - 1] : 0;
+        if (gzi_coff[i] <= pc || gzi_uoff[i] < pu) return fail("the .gzi index is not increasing (entry " + std::to_string(i) + ")");
+        if (gzi_coff[i] > size) return fail("the .gzi index points past the end of the file (entry " + std::to_string(i) + ")");
+    }
+    // the member chain, every .gzi entry on one of its headers with the uncompressed offset the chain gives
+    try {
+        uint64_t coff = 0, u = 0, gi = g0;
+        while (coff < size) {
+            while (gi < n_gzi && gzi_coff[gi] < coff)
+                return fail("the .gzi entry " + std::to_string(gi) + " does not point at a BGZF member header");
+            if (gi < n_gzi && gzi_coff[gi] == coff) {
+                if (gzi_uoff[gi] != u) return fail("the .gzi entry " + std::to_string(gi) + " disagrees with the members' sizes");
+                ++gi;
+            }
+            Member m;
+            uint32_t bsize = 0;
+            if (parse_member(map, size, coff, &m, &bsize) != 0)
+                return fail(member_msg("truncated or malformed", coff) + " (not a complete BGZF file)");
+            m.uoff = u;
+            z->mem.push_back(m);
+            z->uoff.push_back(u);
+            coff += bsize;
+            u += m.isize;
+        }
+        // what is left may only be the end entry (end of the data)
+        for (; gi < n_gzi; ++gi)
+            if (gzi_coff[gi] != size || gzi_uoff[gi] != u) return fail("the .gzi index points past the end of the data");
+        z->total = u;
+        z->slot.assign(z->mem.size(), ~0ull);
+    } catch (...) {
+        return SVX_E_NOMEM;
+    }
+    if (z->mem.empty()) return fail("empty BGZF file");
+    *out = z.release();
+    return SVX_OK;
+}
+
+void z_close(void* p) {
+    Fz* z = static_cast<Fz*>(p);
+    if (!z) return;
+    z->free_device();
+    delete z;
+}
+
+// ------------------------------------------------------------------ host path
+struct Win {
+    uint32_t i;       // window index
+    uint32_t m0, m1;  // first and last member under it
+    uint64_t b0, b1;
+};
+
+int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, bool upper,
+               const uint64_t* out_off, uint8_t* out, int n_threads, std::vector<Win>& wins) {
+    std::sort(wins.begin(), wins.end(), [](const Win& a, const Win& b) { return a.m0 != b.m0 ? a.m0 < b.m0 : a.i < b.i; });
+    {
+        std::lock_guard<std::mutex> lk(z->mu);
+        ++z->stat[5];
+    }
+    size_t w_lo = 0;
+    while (w_lo < wins.size()) {
+        // one group: windows in order of their first member until kGroupMembers distinct members are under them
+        std::vector<uint32_t> ms;
+        size_t w_hi = w_lo;
+        uint32_t last = ~0u;
+        while (w_hi < wins.size()) {
+            const Win& w = wins[w_hi];
+            const uint32_t from = last == ~0u ? w.m0 : std::max(w.m0, last + 1);
+            const uint32_t add = w.m1 >= from ? w.m1 - from + 1 : 0;
+            if (w_hi > w_lo && ms.size() + add > kGroupMembers) break;
+            for (uint32_t m = from; add && m <= w.m1; ++m) ms.push_back(m);
+            last = last == ~0u ? w.m1 : std::max(last, w.m1);
+            ++w_hi;
+        }
+        // (ms: sorted and distinct by construction)  members from the cache, the rest inflated
+        std::vector<Buf> bufs(ms.size());
+        std::vector<uint32_t> todo;
+        {
+            std::lock_guard<std::mutex> lk(z->mu);
+            for (size_t k = 0; k < ms.size(); ++k) {
+                for (const auto& c : z->cache)
+                    if (c.first == ms[k]) { bufs[k] = c.second; break; }
+                if (bufs[k]) ++z->stat[3];
+                else todo.push_back((uint32_t)k);
+            }
+        }
+        std::atomic<size_t> next(0);
+        std::atomic<int64_t> bad(-1);
+        try {
+            for (uint32_t k : todo) bufs[k] = std::make_shared<std::vector<uint8_t>>(z->mem[ms[k]].isize);
+        } catch (...) {
+            return SVX_E_NOMEM;
+        }
+        auto inflate_work = [&]() {
+            for (;;) {
+                const size_t t = next.fetch_add(2);
+                if (t >= todo.size() || bad.load() >= 0) break;
+                const uint32_t ka = todo[t];
+                if (t + 1 < todo.size()) {
+                    const uint32_t kb = todo[t + 1];
+                    bool oa = false, ob = false;
+                    inflate_two(z, ms[ka], bufs[ka]->data(), ms[kb], bufs[kb]->data(), &oa, &ob);
+                    if (!oa) bad.store(ms[ka]);
+                    else if (!ob) bad.store(ms[kb]);
+                } else if (!inflate_member(z, ms[ka], bufs[ka]->data())) {
+                    bad.store(ms[ka]);
+                }
+            }
+        };
+        int rc = run_threads(todo.size() >= 8 ? n_threads : 1, inflate_work);
+        if (rc != SVX_OK) return rc;
+        {
+            std::lock_guard<std::mutex> lk(z->mu);
+            z->stat[0] += todo.size();
+        }
+        if (bad.load() >= 0) {
+            z->set_err(member_msg("damaged or malformed", z->mem[(size_t)bad.load()].coff) + " (CRC32, ISIZE or DEFLATE stream)");
+            return SVX_E_INVALID;
+        }
+        // gather
+        std::atomic<size_t> wnext(w_lo);
+        auto gather_work = [&]() {
+            std::vector<uint8_t> raw;
+            for (;;) {
+                const size_t w = wnext.fetch_add(64);
+                if (w >= w_hi) break;
+                for (size_t j = w; j < std::min(w_hi, w + 64); ++j) {
+                    const Win& W = wins[j];
+                    const size_t nb = (size_t)(W.b1 - W.b0);
+                    raw.resize(nb);
+                    uint64_t u = W.b0;
+                    size_t k = (size_t)(std::lower_bound(ms.begin(), ms.end(), W.m0) - ms.begin());
+                    for (uint32_t m = W.m0; m <= W.m1; ++m, ++k) {
+                        const Member& M = z->mem[m];
+                        const uint64_t hi = std::min<uint64_t>(W.b1, M.uoff + M.isize);
+                        if (hi > u) {
+                            memcpy(raw.data() + (u - W.b0), bufs[k]->data() + (u - M.uoff), (size_t)(hi - u));
+                            u = hi;
+                        }
+                    }
+                    const int64_t e = std::min(end[W.i], g->length[ref[W.i]]);
+                    lines_to_bases(g, ref[W.i], start[W.i], e, upper, raw.data(), nb, out + out_off[W.i]);
+                }
+            }
+        };
+        rc = run_threads(w_hi - w_lo >= 256 ? n_threads : 1, gather_work);
+        if (rc != SVX_OK) return rc;
+        // the group's last members stay cached
+        {
+            std::lock_guard<std::mutex> lk(z->mu);
+            for (size_t k = ms.size() > kCacheMembers ? ms.size() - kCacheMembers : 0; k < ms.size(); ++k) {
+                auto it = std::find_if(z->cache.begin(), z->cache.end(), [&](const std::pair<uint32_t, Buf>& c) { return c.first == ms[k]; });
+                if (it != z->cache.end()) z->cache.erase(it);
+                z->cache.emplace_back(ms[k], bufs[k]);
+            }
+            if (z->cache.size() > kCacheMembers) z->cache.erase(z->cache.begin(), z->cache.end() - (long)kCacheMembers);
+        }
+        w_lo = w_hi;
+    }
+    return SVX_OK;
+}
+
+// ------------------------------------------------------------------ device path
+// 1: done; 0: not taken (the caller runs the host path); < 0: a status to return
+int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, bool upper,
+                 const uint64_t* out_off, uint8_t* out, uint64_t out_lo, uint64_t out_bytes, int n_threads, const std::vector<Win>& wins) {
+    std::lock_guard<std::mutex> lk(z->mu);  // one device call of a handle at a time (arena, scratch, stream)
+    if (z->device < 0 || z->dev_broken || !g_inflate || !g_gather || !g_arena || host_only_env()) return 0;
+    std::vector<uint32_t> ms;
+    for (const Win& w : wins)
+        for (uint32_t m = w.m0; m <= w.m1; ++m) ms.push_back(m);
+    std::sort(ms.begin(), ms.end());
+    ms.erase(std::unique(ms.begin(), ms.end()), ms.end());
+    if (ms.size() < z->dev_min) return 0;
+    auto broken = [&]() {  // the device could not be used: the host path from here on
+        (void)hipGetLastError();
+        z->free_device();
+        z->dev_broken = true;
+        return 0;
+    };
+    if (hipSetDevice(z->device) != hipSuccess) return broken();
+    if (!z->stream && hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) return broken();
+    // the members not resident yet, and room for them in the arena
+    std::vector<uint32_t> fresh;
+    uint64_t fresh_out = 0, in_bytes = 0;
+    for (uint32_t m : ms) {
+        if (z->slot[m] != ~0ull) continue;
+        fresh.push_back(m);
+        fresh_out += ((uint64_t)z->mem[m].isize + 8 + 15) & ~15ull;
+        in_bytes += ((uint64_t)z->mem[m].payload_len + 3) & ~3ull;
+    }
+    z->stat[3] += ms.size() - fresh.size();
+    if (z->arena_used + fresh_out > z->arena_cap) {
+        if (z->arena_used + fresh_out > kArenaCap) return 0;  // (past the cap: this call on the host)
+        uint64_t cap = std::max<uint64_t>(64ull << 20, 2 * z->arena_cap);
+        while (cap < z->arena_used + fresh_out) cap *= 2;
+        cap = std::min(cap, kArenaCap);
+        void* p = nullptr;
+        if (hipMalloc(&p, cap) != hipSuccess) return broken();
+        if (z->arena_used && hipMemcpyAsync(p, z->d_arena, z->arena_used, hipMemcpyDeviceToDevice, z->stream) != hipSuccess) {
+            (void)hipFree(p);
+            return broken();
+        }
+        if (z->d_arena) {
+            (void)hipStreamSynchronize(z->stream);
+            (void)hipFree(z->d_arena);
+        }
+        z->d_arena = static_cast<uint8_t*>(p);
+        z->arena_cap = cap;
+    }
+    // the chunks of the gather: up to SVX_FASTA_CHUNK_BASES bases of a window inside two members
+    std::vector<svx_fasta_chunk> chunks;
+    std::vector<uint64_t> new_slot(fresh.size());
+    {
+        uint64_t at = z->arena_used;
+        for (size_t k = 0; k < fresh.size(); ++k) {
+            new_slot[k] = at;
+            at += ((uint64_t)z->mem[fresh[k]].isize + 8 + 15) & ~15ull;
+        }
+    }
+    bool unplanned = false;  // (a member neither resident nor staged: never, by construction — checked all the same)
+    auto slot_of = [&](uint32_t m) -> uint64_t {
+        if (z->slot[m] != ~0ull) return z->slot[m];
+        const size_t k = (size_t)(std::lower_bound(fresh.begin(), fresh.end(), m) - fresh.begin());
+        if (k == fresh.size() || fresh[k] != m) {
+            unplanned = true;
+            return 0;
+        }
+        return new_slot[k];
+    };
+    for (const Win& w : wins) {
+        const int32_t r = ref[w.i];
+        const uint64_t lb = (uint64_t)g->line_bases[r], lw = (uint64_t)g->line_width[r], off = (uint64_t)g->offset[r];
+        const uint64_t e = (uint64_t)std::min(end[w.i], g->length[r]);
+        uint32_t shift = 0;
+        uint64_t magic = 0;
+        if (e < (1ull << 31) && lb < (1ull << 31)) {
+            uint32_t c = 0;
+            while ((1ull << c) < lb) ++c;
+            shift = 31 + c;
+            magic = ((1ull << shift) / lb) + 1;
+        }
+        uint64_t s = (uint64_t)start[w.i], o = out_off[w.i];
+        while (s < e) {
+            const uint64_t u0 = off + (s / lb) * lw + s % lb;
+            const uint32_t ma = z->member_of(u0);
+            // member b only where the window reaches it (a member behind the window may be neither resident nor staged)
+            const uint32_t nb = z->next_nonempty(ma);
+            const uint32_t mb = nb <= w.m1 ? nb : (uint32_t)z->mem.size();
+            const uint64_t lim = mb < z->mem.size() ? z->mem[mb].uoff + z->mem[mb].isize : z->mem[ma].uoff + z->mem[ma].isize;
+            const uint64_t rel = lim - off;  // bases in front of byte `lim`
+            const uint64_t before = (rel / lw) * lb + std::min<uint64_t>(rel % lw, lb);
+            const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(e, before) - s, SVX_FASTA_CHUNK_BASES);
+            svx_fasta_chunk c;
+            c.out = o;
+            c.off = off;
+            c.s0 = s;
+            c.src_a = slot_of(ma);
+            c.u_a = z->mem[ma].uoff;
+            c.src_b = mb < z->mem.size() ? slot_of(mb) : c.src_a;
+            c.u_b = mb < z->mem.size() ? z->mem[mb].uoff : ~0ull;
+            c.magic = magic;
+            c.shift = shift;
+            c.n = (uint32_t)n;
+            c.line_bases = (uint32_t)lb;
+            c.line_width = (uint32_t)lw;
+            chunks.push_back(c);
+            s += n;
+            o += n;
+        }
+    }
+    if (unplanned) return 0;
+    // scratch: payloads | in_off | out_off (u64) | in_len | isize | crc | status | n_tok (u32) | chunks | packed output | tokens
+    const uint32_t nf = (uint32_t)fresh.size();
+    auto up256 = [](uint64_t x) { return (x + 255) & ~255ull; };
+    const uint32_t arena_members = std::min<uint32_t>(nf, std::max<uint32_t>(1u, g_arena()));
+    const uint64_t o_in = 0, o_tab = up256(in_bytes + 8);
+    const uint64_t tab_bytes = (uint64_t)nf * 16 + (uint64_t)nf * 12;
+    const uint64_t o_status = o_tab + up256(tab_bytes), o_ntok = o_status + up256((uint64_t)nf * 4);
+    const uint64_t o_chunks = o_ntok + up256((uint64_t)nf * 4);
+    const uint64_t o_packed = o_chunks + up256(chunks.size() * sizeof(svx_fasta_chunk));
+    const uint64_t o_tok = o_packed + up256(out_bytes + 8);
+    const uint64_t need = o_tok + (nf ? up256((uint64_t)arena_members * SVX_INFLATE_TOK_STRIDE * 8) : 0);
+    const uint64_t stage_need = o_chunks + chunks.size() * sizeof(svx_fasta_chunk);  // everything that goes up
+    if (z->scratch_cap < need) {
+        if (z->d_scratch) {
+            (void)hipStreamSynchronize(z->stream);
+            (void)hipFree(z->d_scratch);
+        }
+        z->d_scratch = nullptr;
+        z->scratch_cap = 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, need + (need >> 3)) != hipSuccess) return broken();
+        z->d_scratch = static_cast<uint8_t*>(p);
+        z->scratch_cap = need + (need >> 3);
+    }
+    if (z->stage_cap < std::max(stage_need, out_bytes)) {
+        (void)hipStreamSynchronize(z->stream);
+        if (z->h_stage) (void)hipHostFree(z->h_stage);
+        z->h_stage = nullptr;
+        z->stage_cap = 0;
+        const uint64_t want = std::max(stage_need, out_bytes);
+        void* p = nullptr;
+        if (hipHostMalloc(&p, want + (want >> 3), hipHostMallocDefault) != hipSuccess) return broken();
+        z->h_stage = static_cast<uint8_t*>(p);
+        z->stage_cap = want + (want >> 3);
+    }
+    // stage: the payloads (by the threads), the tables, the chunks
+    uint8_t* h = z->h_stage;
+    std::vector<uint64_t> in_off(nf);
+    {
+        uint64_t at = 0;
+        for (uint32_t k = 0; k < nf; ++k) {
+            in_off[k] = at;
+            at += ((uint64_t)z->mem[fresh[k]].payload_len + 3) & ~3ull;
+        }
+    }
+    std::atomic<uint32_t> next(0);
+    auto stage = [&]() {
+        for (;;) {
+            const uint32_t k0 = next.fetch_add(64);
+            if (k0 >= nf) break;
+            for (uint32_t k = k0; k < std::min(nf, k0 + 64); ++k) {
+                const Member& M = z->mem[fresh[k]];
+                memcpy(h + o_in + in_off[k], z->map + M.coff + M.payload_off, M.payload_len);
+            }
+        }
+    };
+    int rc = run_threads(nf >= 256 ? n_threads : 1, stage);
+    if (rc != SVX_OK) return rc;
+    uint64_t* t_in_off = reinterpret_cast<uint64_t*>(h + o_tab);
+    uint64_t* t_out_off = t_in_off + nf;
+    uint32_t* t_in_len = reinterpret_cast<uint32_t*>(t_out_off + nf);
+    uint32_t* t_isize = t_in_len + nf;
+    uint32_t* t_crc = t_isize + nf;
+    for (uint32_t k = 0; k < nf; ++k) {
+        const Member& M = z->mem[fresh[k]];
+        t_in_off[k] = in_off[k];
+        t_out_off[k] = new_slot[k];
+        t_in_len[k] = M.payload_len;
+        t_isize[k] = M.isize;
+        t_crc[k] = M.crc;
+    }
+    if (!chunks.empty()) memcpy(h + o_chunks, chunks.data(), chunks.size() * sizeof(svx_fasta_chunk));
+    uint8_t* d = z->d_scratch;
+    bool ok = hipMemcpyAsync(d, h, stage_need, hipMemcpyHostToDevice, z->stream) == hipSuccess;
+    z->stat[2] += in_bytes;
+    if (ok && nf)
+        ok = g_inflate(z->stream, d + o_in, reinterpret_cast<const uint64_t*>(d + o_tab), reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 16),
+                       reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 20), reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 24), nf,
+                       z->d_arena, reinterpret_cast<const uint64_t*>(d + o_tab + (uint64_t)nf * 8), reinterpret_cast<uint32_t*>(d + o_status),
+                       reinterpret_cast<uint32_t*>(d + o_ntok), d + o_tok, arena_members) == 0;
+    ok = ok && g_gather(z->stream, z->d_arena, reinterpret_cast<const svx_fasta_chunk*>(d + o_chunks), (uint32_t)chunks.size(),
+                        upper ? 1 : 0, d + o_packed) == 0;
+    std::vector<uint32_t> status(nf);
+    ok = ok && (nf == 0 || hipMemcpyAsync(status.data(), d + o_status, (size_t)nf * 4, hipMemcpyDeviceToHost, z->stream) == hipSuccess);
+    ok = ok && (out_bytes == out_lo ||
+                hipMemcpyAsync(h + out_lo, d + o_packed + out_lo, out_bytes - out_lo, hipMemcpyDeviceToHost, z->stream) == hipSuccess);
+    ok = ok && hipStreamSynchronize(z->stream) == hipSuccess;
+    if (!ok) return broken();  // (the host path takes the call; nothing of it was written yet)
+    for (uint32_t k = 0; k < nf; ++k)
+        if (status[k] != 0) {
+            // nothing of this call becomes resident: the arena ends where it did
+            z->err = member_msg("damaged or malformed", z->mem[fresh[k]].coff) + " (CRC32, ISIZE or DEFLATE stream; device)";
+            return SVX_E_INVALID;
+        }
+    for (uint32_t k = 0; k < nf; ++k) z->slot[fresh[k]] = new_slot[k];
+    if (nf) z->arena_used = new_slot[nf - 1] + (((uint64_t)z->mem[fresh[nf - 1]].isize + 8 + 15) & ~15ull);
+    z->stat[1] += nf;
+    ++z->stat[4];
+    if (out_bytes > out_lo) memcpy(out + out_lo, h + out_lo, out_bytes - out_lo);
+    return 1;
+}
+
+int z_fetch(void* p, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, uint32_t n, int upper,
+            const uint64_t* out_off, uint8_t* out, int n_threads) {
+    Fz* z = static_cast<Fz*>(p);
+    if (n_threads <= 0) n_threads = (int)std::min<unsigned>(16u, std::max<unsigned>(1u, std::thread::hardware_concurrency()));
+    n_threads = std::min(n_threads, 16);
+    std::vector<Win> wins;
+    try {
+        wins.reserve(n);
+    } catch (...) {
+        return SVX_E_NOMEM;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const int32_t r = ref[i];
+        const int64_t e = std::min(end[i], g->length[r]);
+        if (e <= start[i]) continue;
+        if (g->line_bases[r] <= 0 || g->line_width[r] < g->line_bases[r] || g->offset[r] < 0) {
+            z->set_err("bad .fai geometry");
+            return SVX_E_INVALID;
+        }
+        Win w;
+        w.i = i;
+        byte_range(g, r, start[i], e, &w.b0, &w.b1);
+        if (w.b1 > z->total || w.b1 <= w.b0) {
+            z->set_err("reference windows shorter than the index says");
+            return SVX_E_INVALID;
+        }
+        w.m0 = z->member_of(w.b0);
+        w.m1 = z->member_of(w.b1 - 1);
+        wins.push_back(w);
+    }
+    if (wins.empty()) return SVX_OK;
+    const int d = device_fetch(z, g, ref, start, end, upper != 0, out_off, out, out_off[0], out_off[n], n_threads, wins);
+    if (d < 0) return d;
+    if (d == 1) return SVX_OK;
+    return host_fetch(z, g, ref, start, end, upper != 0, out_off, out, n_threads, wins);
+}
+
+int z_set_device(void* p, int device, uint32_t min_members) {
+    Fz* z = static_cast<Fz*>(p);
+    std::lock_guard<std::mutex> lk(z->mu);
+    if (device != z->device) {
+        z->free_device();
+        z->dev_broken = false;
+    }
+    z->device = device < 0 ? -1 : device;
+    z->dev_min = min_members;
+    return SVX_OK;
+}
+
+void z_stats(const void* p, uint64_t* out) {
+    const Fz* z = static_cast<const Fz*>(p);
+    std::lock_guard<std::mutex> lk(z->mu);
+    for (int k = 0; k < SVX_FASTA_STATS; ++k) out[k] = z->stat[k];
+}
+
+const char* z_last_error(const void* p) {
+    // a copy owned by the calling thread: another thread's failing fetch may replace the handle's message meanwhile
+    thread_local std::string copy;
+    const Fz* z = static_cast<const Fz*>(p);
+    std::lock_guard<std::mutex> lk(z->mu);
+    copy = z->err;
+    return copy.c_str();
+}
+
+const svx_fasta_bgzf_ops kOps = {z_open, z_close, z_fetch, z_set_device, z_stats, z_last_error};
+[[maybe_unused]] const int kRegistered = (svx_fasta_register_bgzf(&kOps), 0);
+
+}  // namespace
+
+extern "C" void svx_fasta_register_device(svx_inflate_launch_fn inflate, svx_fasta_gather_fn gather, svx_inflate_arena_fn arena) {
+    g_inflate = inflate;
+    g_gather = gather;
+    g_arena = arena;
+}

@@ -1574,6 +1574,7 @@ static std::atomic<uint32_t> g_arena_members{SVX_INFLATE_ARENA_MEMBERS};
 extern "C" uint32_t svx_bgzf_inflate_set_arena(uint32_t members) {
     return g_arena_members.exchange(members ? members : SVX_INFLATE_ARENA_MEMBERS);
 }
+uint32_t svx_bgzf_inflate_arena_members() { return g_arena_members.load(); }
 
 // The launches of the two-pass forms: the token lists live in an arena of `tok_members` slices (kTokStride slots of 8 bytes
 // each), so the members go out `tok_members` at a time, one slice of launches behind the other on the stream.

@@ -19,6 +19,7 @@
 
 #include "svx.h"
 #include "svx_text.h"
+#include "svx_fasta_bgzf.h"
 #include <sys/mman.h>
 
 // ------------------------------------------------------------------------------------------ FASTA
@@ -31,7 +32,12 @@ struct svx_fasta {
     size_t size = 0;
     std::vector<int64_t> length, offset;
     std::vector<int32_t> line_bases, line_width;
+    void* z = nullptr;  // a bgzip-compressed file (svx_fasta_open_bgzf): the state svx_fasta_bgzf.cpp keeps; null: plain text
 };
+
+// the compressed form, registered by svx_fasta_bgzf.cpp when the library loads (a build of this file alone has none)
+static const svx_fasta_bgzf_ops* g_bgzf = nullptr;
+extern "C" void svx_fasta_register_bgzf(const svx_fasta_bgzf_ops* ops) { g_bgzf = ops; }
 
 static void set_err(char* err, size_t cap, const char* fmt, const char* a) {
     if (err && cap) snprintf(err, cap, fmt, a);
@@ -78,8 +84,62 @@ extern "C" int svx_fasta_open(const char* path, int32_t n_refs, const int64_t* l
     return SVX_OK;
 }
 
+extern "C" int svx_fasta_open_bgzf(const char* path, int32_t n_refs, const int64_t* length, const int64_t* offset,
+                                   const int32_t* line_bases, const int32_t* line_width, const uint64_t* gzi_coff,
+                                   const uint64_t* gzi_uoff, uint64_t n_gzi, svx_fasta** out, char* err, size_t err_cap) {
+    if (out) *out = nullptr;
+    if (!g_bgzf) {
+        set_err(err, err_cap, "%s", "svx_fasta_open_bgzf: this build reads no bgzip-compressed FASTA");
+        return SVX_E_INVALID;
+    }
+    if (n_gzi && (!gzi_coff || !gzi_uoff)) {
+        set_err(err, err_cap, "%s", "svx_fasta_open_bgzf: bad argument");
+        return SVX_E_INVALID;
+    }
+    svx_fasta* fa = nullptr;
+    int rc = svx_fasta_open(path, n_refs, length, offset, line_bases, line_width, &fa, err, err_cap);
+    if (rc != SVX_OK) return rc;
+    if (!fa->map && fa->size) {  // (SVX_FASTA_PREAD: the members are read from the mapping all the same)
+        void* m = mmap(nullptr, fa->size, PROT_READ, MAP_PRIVATE, fa->fd, 0);
+        if (m != MAP_FAILED) fa->map = static_cast<const uint8_t*>(m);
+    }
+    if (!fa->map) {
+        set_err(err, err_cap, "cannot map %s", path);
+        svx_fasta_close(fa);
+        return SVX_E_INVALID;
+    }
+    rc = g_bgzf->open(fa->map, fa->size, gzi_coff, gzi_uoff, n_gzi, &fa->z, err, err_cap);
+    if (rc != SVX_OK) {
+        svx_fasta_close(fa);
+        return rc;
+    }
+    *out = fa;
+    return SVX_OK;
+}
+
+extern "C" int svx_fasta_is_bgzf(const svx_fasta* fa) { return fa && fa->z ? 1 : 0; }
+
+extern "C" int svx_fasta_set_device(svx_fasta* fa, int device, uint32_t min_members) {
+    if (!fa) return SVX_E_INVALID;
+    if (!fa->z) return SVX_OK;  // plain text: nothing to inflate
+    return g_bgzf->set_device(fa->z, device, min_members);
+}
+
+extern "C" int svx_fasta_stats(const svx_fasta* fa, uint64_t* out) {
+    if (!fa || !out) return SVX_E_INVALID;
+    for (int k = 0; k < SVX_FASTA_STATS; ++k) out[k] = 0;
+    if (fa->z) g_bgzf->stats(fa->z, out);
+    return SVX_OK;
+}
+
+extern "C" const char* svx_fasta_last_error(const svx_fasta* fa) {
+    if (!fa) return "null handle";
+    return fa->z ? g_bgzf->last_error(fa->z) : "";
+}
+
 extern "C" void svx_fasta_close(svx_fasta* fa) {
     if (!fa) return;
+    if (fa->z) g_bgzf->close(fa->z);
     if (fa->map) munmap(const_cast<uint8_t*>(fa->map), fa->size);
     if (fa->fd >= 0) close(fa->fd);
     delete fa;
@@ -136,6 +196,10 @@ extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, co
         if (out_off[i + 1] < out_off[i] || (int64_t)(out_off[i + 1] - out_off[i]) != len) return SVX_E_INVALID;
     }
     if (n && out_off[n] && !out) return SVX_E_INVALID;
+    if (fa->z) {
+        const svx_fasta_geom g{n_refs, fa->length.data(), fa->offset.data(), fa->line_bases.data(), fa->line_width.data()};
+        return g_bgzf->fetch(fa->z, &g, ref, start, end, n, upper, out_off, out, n_threads);
+    }
     if (n_threads <= 0) n_threads = (int)std::min<unsigned>(16u, std::max<unsigned>(1u, std::thread::hardware_concurrency()));
     if (n < 256) n_threads = 1;
     std::atomic<uint32_t> next(0);
