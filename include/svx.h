@@ -519,6 +519,30 @@ int svx_bgzf_inflate_set_two_pass(int on);
  * costs at least one member's decode latency — and what the tests use to run many slices over few members. */
 uint32_t svx_bgzf_inflate_set_arena(uint32_t members);
 
+/*
+ * BGZF compression (svx_deflate.hip), the counterpart of svx_bgzf_inflate_dev: the input is cut into blocks of 65 280
+ * bytes (htslib's BGZF_BLOCK_SIZE, the last one shorter) and each becomes one gzip member with the BC extra field
+ * (BSIZE), raw DEFLATE with dynamic Huffman codes (or a stored block where that would not be smaller: every member is at
+ * most 65 536 bytes), CRC32 and ISIZE; the 28-byte EOF member follows.  One workgroup per block; the bytes depend on the
+ * input alone.
+ *
+ * svx_bgzf_deflate_dev: the members of d_in[0 .. n) back to back at d_out (cap >= svx_bgzf_deflate_bound(n), else
+ * SVX_E_CAPACITY), then the EOF member; d_member_len[i] = size of member i (ceil(n / 65280) entries), *d_total (device)
+ * = bytes written.  n = 0: the EOF member alone.  Enqueued on the context's stream, no synchronisation.
+ */
+uint64_t svx_bgzf_deflate_bound(uint64_t n);
+int svx_bgzf_deflate_dev(svx_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t cap,
+                         uint32_t* d_member_len, uint64_t* d_total);
+/* Blocks per launch of svx_bgzf_deflate_dev (default 2048; 0: back to the default); returns the previous value. */
+uint32_t svx_bgzf_deflate_set_slice(uint32_t blocks);
+/* The same container from host bytes: ctx != NULL on that context's device and stream (svx_bgzf_deflate_dev; the
+ * context's staging buffers), ctx == NULL with zlib (raw deflate, level 6) on n_threads host threads (<= 0: one per
+ * hardware thread, at most 16).  *out (out_len bytes, EOF member included) and *member_len (*n_members data members)
+ * are allocated by the library: free both with svx_bgzf_free.  Thread-safe across contexts. */
+int svx_bgzf_compress(svx_ctx* ctx, const uint8_t* src, uint64_t n, int n_threads, uint8_t** out, uint64_t* out_len,
+                      uint32_t** member_len, uint64_t* n_members);
+void svx_bgzf_free(void* p);
+
 /* ------------------------------------------------------------ a5 + a6 ------ */
 /*
  * Pair sort + partition: form_partitions (SVIM_COMBINE.py:15-32).

@@ -142,6 +142,23 @@ void svx_vcf_free(char* text);
  * pwrite at its final place — no joined buffer, the copies into the page cache run side by side.  The position of
  * `fd` is left behind the last line.  n_bytes receives the bytes written. */
 int svx_vcf_write(const svx_vcf_in* in, int fd, uint64_t* n_bytes, uint64_t* n_lines);
+/* The same lines into one buffer of the library's behind a copy of prefix[n_prefix] (the header lines): *text holds
+ * n_prefix + *n_bytes bytes; free with svx_vcf_free. */
+int svx_vcf_format_after(const svx_vcf_in* in, const char* prefix, uint64_t n_prefix, char** text, uint64_t* n_bytes,
+                         uint64_t* n_lines);
+
+/* ------------------------------------------------------------------ tabix ---- */
+/*
+ * The tabix index (VCF preset: sequence column 1, begin 2, end from REF and INFO/END, meta '#') of `text` compressed
+ * into BGZF members of 65 280 input bytes each whose sizes are member_len[n_members] (svx_bgzf_compress's).  The
+ * index's uncompressed bytes (BGZF-compress them to write the file) in *index, freed with svx_vcf_free; *kind = 1 for
+ * a .tbi (min_shift 14, 5 levels), 2 for a .csi (min_shift 14, depth 6) when a record ends beyond 2^29, 0 when the
+ * records cannot be indexed — a contig's records not contiguous, or positions that decrease within one: *index stays
+ * NULL and err names the first such record.  Names are listed in order of first appearance; the pseudo-bin carries
+ * the first / last offsets and the record counts.  Malformed lines: SVX_E_INVALID with err set.
+ */
+int svx_tabix_build(const uint8_t* text, uint64_t n, const uint32_t* member_len, uint64_t n_members, uint8_t** index,
+                    uint64_t* index_len, int* kind, char* err, size_t err_cap);
 
 #ifdef __cplusplus
 }

@@ -719,10 +719,12 @@ def _pool_of_strings(strings):
     return b"".join(enc), off
 
 
-def vcf_body(table, types_to_output, reference, options, sink=None):
+def vcf_body(table, types_to_output, reference, options, sink=None, prefix=None):
     """The record lines of write_final_vcf (:428-477) for the rows of `table` as bytes (every line ends with a
     newline): entries in the reference's list order, formatted, naturally sorted and numbered by
-    svx_vcf_format.  With `sink` (a binary file object) the lines are written to it instead of being returned."""
+    svx_vcf_format.  With `sink` (a binary file object) the lines are written to it instead of being returned.
+    With `prefix` (bytes): (address, length) of ONE buffer of the library's holding prefix + lines (svx_vcf_format_after;
+    release it with svx_vcf_free), or None when there are no lines."""
     lib = _lib.load()
     t = table
     for k in [k for k in LAST_TIMING if k.startswith("vcf_")]:
@@ -786,7 +788,7 @@ def vcf_body(table, types_to_output, reference, options, sink=None):
         reference.close()  # (:466-467)
         tc = _clock("vcf_reference_close_s", tc)
     if ne == 0:
-        return b"" if sink is None else None
+        return b"" if sink is None and prefix is None else None
     natural = _natural_ranks(set(t.contigs))
     contig_rank = np.array([natural[c] for c in t.contigs], dtype=np.int32)
     contig_pool, contig_off = _pool_of_strings(t.contigs)
@@ -833,6 +835,12 @@ def vcf_body(table, types_to_output, reference, options, sink=None):
         sink.seek(0, os.SEEK_END)
         _clock("vcf_format_s", tc)
         return None
+    if prefix is not None:  # the header and the lines in one buffer: what the BGZF compressor reads (--bgzip_output)
+        rc = lib.svx_vcf_format_after(C.byref(arg), prefix, len(prefix), C.byref(text), C.byref(n_bytes), C.byref(n_lines))
+        if rc != 0:
+            raise _lib.SvxError(rc, "svx_vcf_format_after")
+        _clock("vcf_format_s", tc)
+        return text.value, len(prefix) + n_bytes.value
     rc = lib.svx_vcf_format(C.byref(arg), C.byref(text), C.byref(n_bytes), C.byref(n_lines))
     if rc != 0:
         raise _lib.SvxError(rc, "svx_vcf_format")
@@ -847,10 +855,19 @@ def vcf_body(table, types_to_output, reference, options, sink=None):
         _clock("vcf_write_s", tc)
 
 
-def write_vcf_table(table, version, contig_names, contig_lengths, types_to_output, reference, options, release_reference=True):
+def write_vcf_table(table, version, contig_names, contig_lengths, types_to_output, reference, options, release_reference=True,
+                    ctx=None):
     """write_final_vcf for a CandidateTable (rows of each type in the order the reference's per-type lists have).
     release_reference=False: the mappings of the reference genome, closed inside (:466-467), are left to the end of the
-    process — what the command does, which exits right behind the VCF."""
+    process — what the command does, which exits right behind the VCF.
+    With options.bgzip_output: variants.vcf.gz and its tabix index instead (vcf_bgzf), compressed on `ctx`'s device
+    (None: the process's context of options.device) or on the host threads (SVX_VCF_BGZF_DEVICE)."""
+    if getattr(options, "bgzip_output", False):
+        _write_vcf_bgzf(table, version, contig_names, contig_lengths, types_to_output, reference, options, ctx)
+        if release_reference:
+            from svim_asm_amd import fasta
+            fasta.release_deferred()
+        return
     path = options.working_dir + "/variants.vcf"
     try:
         with open(path, "wb") as vcf_output:
@@ -866,6 +883,32 @@ def write_vcf_table(table, version, contig_names, contig_lengths, types_to_outpu
     if release_reference:
         from svim_asm_amd import fasta
         fasta.release_deferred()  # the genome's mapping, closed inside vcf_body (:466-467), goes away behind the file, on a thread
+
+
+def _write_vcf_bgzf(table, version, contig_names, contig_lengths, types_to_output, reference, options, ctx):
+    from svim_asm_amd import vcf_bgzf
+    path = options.working_dir + "/variants.vcf.gz"
+    lib = _lib.load()
+    buf = None
+    try:
+        header = "".join(line + "\n" for line in _header_lines(version, contig_names, contig_lengths, types_to_output, options))
+        header = header.encode("utf-8", "surrogateescape")
+        buf = vcf_body(table, types_to_output, reference, options, prefix=header)
+        if ctx is None and vcf_bgzf.device_path_wanted():
+            ctx = _lib.default_context(getattr(options, "device", 0) or 0)
+        tc = _clock_start()
+        vcf_bgzf.write(path, buf if buf is not None else header, ctx)
+        _clock("vcf_bgzf_s", tc)
+    except BaseException:
+        # a damaged member of a bgzip-compressed genome under an allele, a device error, a failed write: neither the
+        # compressed VCF nor an index is left
+        for p in (path, path + ".tbi", path + ".csi"):
+            if os.path.exists(p):
+                os.remove(p)
+        raise
+    finally:
+        if buf is not None:
+            lib.svx_vcf_free(buf[0])
 
 
 def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_duplication_candidates,

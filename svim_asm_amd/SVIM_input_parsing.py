@@ -43,6 +43,8 @@ _OUTPUT = [
     ("--interspersed_duplications_as_insertions", dict(action="store_true", help="Represent interspersed "
                                                                                  "duplications as insertions")),
     ("--query_names", dict(action="store_true", help="Output names of supporting query sequences in INFO/READS")),
+    ("--bgzip_output", dict(action="store_true", help="Write variants.vcf.gz (bgzip-compressed) and its tabix index "
+                                                      "instead of variants.vcf")),
 ]
 
 

@@ -212,6 +212,16 @@ SYMBOLS = {
     "svx_vcf_format": (C.c_int, [C.POINTER(VcfIn), C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "svx_vcf_free": (None, [_P]),
     "svx_vcf_write": (C.c_int, [C.POINTER(VcfIn), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "svx_vcf_format_after": (C.c_int, [C.POINTER(VcfIn), _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
+    "svx_bgzf_deflate_bound": (C.c_uint64, [C.c_uint64]),
+    "svx_bgzf_deflate_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
+    "svx_bgzf_deflate_set_slice": (C.c_uint32, [C.c_uint32]),
+    "svx_bgzf_compress": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P),
+                                    C.POINTER(C.c_uint64)]),
+    "svx_bgzf_free": (None, [_P]),
+    "svx_tabix_build": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                                  C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -356,6 +366,12 @@ class Context:
         for x in d + [d_out, d_st]:
             x.free()
         return status, outs, ms
+
+    def bgzf_deflate(self, data):
+        """`data` (bytes-like) as BGZF on the device (svx_bgzf_compress on this context: svx_bgzf_deflate_dev's kernel).
+        Returns (the compressed bytes with the EOF member, sizes of the data members as a uint32 array)."""
+        from svim_asm_amd import vcf_bgzf
+        return vcf_bgzf.compress(data, ctx=self)
 
     def hbm_read_probe(self, d_ptr, nbytes, reps=5):
         """GB/s of a read-only nontemporal stream over a resident buffer (svx_hbm_read_probe_dev)."""

@@ -177,9 +177,9 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
         _ = candidates.seqs, [t.seqs for t in mine]
         _timeline.mark("PAIR done", sample=first_no + k)
         write_vcf_table(candidates, cli.__version__, mine_files[0].references, mine_files[0].lengths,
-                        [entry.strip() for entry in o.types.split(",")], reference, o)
+                        [entry.strip() for entry in o.types.split(",")], reference, o, ctx=ctx)
         _timeline.mark("VCF written", sample=first_no + k)
-        logging.info("sample %d of %d: %s/variants.vcf", first_no + k + 1, n_total, wd)
+        logging.info("sample %d of %d: %s/variants.vcf%s", first_no + k + 1, n_total, wd, ".gz" if getattr(o, "bgzip_output", False) else "")
     for f in files:
         f.close()
     del tables, files

@@ -1547,6 +1547,8 @@ static const uint32_t (*crc_shift_columns())[32] {
     return cols;
 }
 
+const uint32_t (*svx_crc32_shift_columns())[32] { return crc_shift_columns(); }
+
 #ifdef SVX_WPARSE_STATS
 extern "C" int svx_debug_wparse_stats(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wstats), sizeof(unsigned long long) * 16) != hipSuccess) return -1;

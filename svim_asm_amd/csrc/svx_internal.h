@@ -134,6 +134,9 @@ int svx_bgzf_inflate_on_stream(void* stream, const uint8_t* d_in, const uint64_t
 uint32_t svx_bgzf_inflate_arena_members();  // svx_bgzf_inflate_set_arena's current value
 int svx_gather_ranges_on_stream(void* stream, const uint8_t* d_src, const uint64_t* d_src_off, const uint32_t* d_len,
                                 const uint64_t* d_dst_off, uint32_t n, uint8_t* d_dst);
+// the operators x -> x * z^(8 * 1024 * 2^j), j = 0..5, of the CRC-32 state as 32 columns each (svx_inflate.hip; the
+// folds of per-lane CRC pieces in svx_inflate.hip and svx_deflate.hip)
+const uint32_t (*svx_crc32_shift_columns())[32];
 int svx_wait_blocking(svx_ctx* ctx);
 int svx_timing_begin(svx_ctx* ctx);           // records ev[0]
 int svx_timing_mark(svx_ctx* ctx, int which); // records ev[which] (1: dominant start, 2: dominant end)

@@ -293,7 +293,8 @@ int pwrite_all(int fd, const char* p, size_t n, uint64_t at) {
 // fd < 0: joined into one malloc'ed buffer (*text).  fd >= 0: every thread writes its own chunk at its place in the
 // file (pwrite at `file_at` + the sizes of the chunks in front of it) — no joined copy, and the copies into the page
 // cache run side by side.
-int vcf_format_impl(const svx_vcf_in* in, char** text, int fd, uint64_t file_at, uint64_t* n_bytes, uint64_t* n_lines) {
+int vcf_format_impl(const svx_vcf_in* in, char** text, int fd, uint64_t file_at, uint64_t* n_bytes, uint64_t* n_lines,
+                    const char* prefix = nullptr, uint64_t n_prefix = 0) {
     if (!in || !n_bytes || (fd < 0 && !text)) return SVX_E_INVALID;
     if (text) *text = nullptr;
     *n_bytes = 0;
@@ -588,11 +589,12 @@ int vcf_format_impl(const svx_vcf_in* in, char** text, int fd, uint64_t file_at,
             if (n_lines) *n_lines = ne;
             return SVX_OK;
         }
-        char* buf = (char*)malloc(total ? total : 1);
+        char* buf = (char*)malloc(n_prefix + total ? n_prefix + total : 1);
         if (!buf) return SVX_E_NOMEM;
+        if (n_prefix) memcpy(buf, prefix, n_prefix);
         {
             std::vector<size_t> at(n_thr);
-            size_t pos = 0;
+            size_t pos = n_prefix;
             for (unsigned t = 0; t < n_thr; ++t) { at[t] = pos; pos += parts[t].s.size(); }
             auto copy = [&](unsigned t) { if (parts[t].s.size()) memcpy(buf + at[t], parts[t].s.data(), parts[t].s.size()); };
             if (n_thr == 1) {
@@ -634,4 +636,200 @@ extern "C" int svx_vcf_write(const svx_vcf_in* in, int fd, uint64_t* n_bytes, ui
     return lseek(fd, here + (off_t)n, SEEK_SET) < 0 ? SVX_E_INVALID : SVX_OK;
 }
 
+extern "C" int svx_vcf_format_after(const svx_vcf_in* in, const char* prefix, uint64_t n_prefix, char** text, uint64_t* n_bytes,
+                                    uint64_t* n_lines) {
+    if (!text || (n_prefix && !prefix)) return SVX_E_INVALID;
+    return vcf_format_impl(in, text, -1, 0, n_bytes, n_lines, prefix, n_prefix);
+}
+
 extern "C" void svx_vcf_free(char* text) { free(text); }
+
+// ------------------------------------------------------------------------------------------ tabix / CSI index
+// The index of a bgzip-compressed VCF (hts-specs tabix.pdf and CSIv1.pdf; htslib's tbx_parse1 for the VCF preset).
+namespace {
+
+constexpr uint64_t kBgzfBlock = 65280;
+
+struct TbxChunk { uint64_t beg, end; };
+struct TbxRef {
+    std::string name;
+    std::vector<std::pair<uint32_t, std::vector<TbxChunk>>> bins;  // in order of first use
+    std::vector<int64_t> bin_at;   // bin -> index into bins (-1)
+    std::vector<uint64_t> ioff;    // linear index (UINT64_MAX: empty window)
+    uint64_t first = 0, last = 0, n_rec = 0;
+    int64_t last_beg = -1;
+};
+
+uint32_t reg2bin(int64_t beg, int64_t end, int min_shift, int depth) {
+    int l = depth, s = min_shift, t = ((1 << depth * 3) - 1) / 7;
+    for (--end; l > 0; --l, s += 3, t -= 1 << l * 3)
+        if (beg >> s == end >> s) return (uint32_t)(t + (beg >> s));
+    return 0;
+}
+
+void put32(std::string& o, uint32_t v) { o.append(reinterpret_cast<const char*>(&v), 4); }
+void put64(std::string& o, uint64_t v) { o.append(reinterpret_cast<const char*>(&v), 8); }
+
+}  // namespace
+
+extern "C" int svx_tabix_build(const uint8_t* text, uint64_t n, const uint32_t* member_len, uint64_t n_members, uint8_t** index,
+                               uint64_t* index_len, int* kind, char* err, size_t err_cap) {
+    if (!index || !index_len || !kind || (n && !text) || (n_members && !member_len) || n_members < (n + kBgzfBlock - 1) / kBgzfBlock)
+        return SVX_E_INVALID;
+    *index = nullptr;
+    *index_len = 0;
+    *kind = 0;
+    if (err && err_cap) err[0] = 0;
+    try {
+        std::vector<uint64_t> coff(n_members + 1, 0);
+        for (uint64_t i = 0; i < n_members; ++i) coff[i + 1] = coff[i] + member_len[i];
+        auto voff = [&](uint64_t u) { return coff[u / kBgzfBlock] << 16 | (u % kBgzfBlock); };
+        struct Rec { uint32_t ref; int64_t beg, end; uint64_t vb, ve; };
+        std::vector<TbxRef> refs;
+        std::vector<Rec> recs;
+        int64_t max_end = 0;
+        int32_t cur = -1;
+        auto bad_line = [&](uint64_t at, uint64_t e, const char* what) {
+            if (err && err_cap) snprintf(err, err_cap, "%s: %.*s", what, (int)std::min<uint64_t>(e - at, 200), (const char*)text + at);
+        };
+        for (uint64_t at = 0; at < n;) {
+            const uint8_t* nl = static_cast<const uint8_t*>(memchr(text + at, '\n', n - at));
+            const uint64_t e = nl ? (uint64_t)(nl - text) : n, next = nl ? e + 1 : n;
+            if (e == at || text[at] == '#') { at = next; continue; }
+            // columns 1 (CHROM), 2 (POS), 4 (REF), 8 (INFO)
+            uint64_t col[9], ncol = 0, p = at;
+            col[ncol++] = at;
+            while (ncol < 9 && p < e) {
+                if (text[p] == '\t') col[ncol++] = p + 1;
+                ++p;
+            }
+            if (ncol < 8) { bad_line(at, e, "a VCF line with fewer than 8 columns"); return SVX_E_INVALID; }
+            auto col_end = [&](int c) { return c + 1 < (int)ncol ? col[c + 1] - 1 : e; };
+            const std::string name(reinterpret_cast<const char*>(text) + col[0], col_end(0) - col[0]);
+            int64_t pos = 0;
+            for (uint64_t q = col[1]; q < col_end(1); ++q) {
+                if (text[q] < '0' || text[q] > '9') { bad_line(at, e, "a VCF line whose POS is not a number"); return SVX_E_INVALID; }
+                pos = pos * 10 + (text[q] - '0');
+                if (pos > (1ll << 40)) { bad_line(at, e, "a POS out of range"); return SVX_E_INVALID; }
+            }
+            const int64_t beg = pos - 1;
+            int64_t end = beg + (int64_t)(col_end(3) - col[3]);
+            // INFO/END, at the start of INFO or behind a ';'
+            for (uint64_t q = col[7], qe = col_end(7); q + 4 <= qe; ++q) {
+                if ((q == col[7] || text[q - 1] == ';') && !memcmp(text + q, "END=", 4)) {
+                    uint64_t v = q + 4;
+                    if (v < qe && text[v] == '.') break;
+                    int64_t x = 0;
+                    bool any = false;
+                    while (v < qe && text[v] >= '0' && text[v] <= '9' && x < (1ll << 40)) { x = x * 10 + (text[v] - '0'); ++v; any = true; }
+                    if (any && x > beg) end = x;
+                    break;
+                }
+            }
+            if (end <= beg) end = beg + 1;
+            if (cur < 0 || refs[cur].name != name) {
+                int32_t found = -1;
+                for (size_t r = 0; r < refs.size(); ++r)
+                    if (refs[r].name == name) found = (int32_t)r;
+                if (found >= 0) {
+                    if (kind) *kind = 0;
+                    bad_line(at, e, "records of a contig are not contiguous");
+                    return SVX_OK;
+                }
+                refs.emplace_back();
+                refs.back().name = name;
+                cur = (int32_t)refs.size() - 1;
+            }
+            if (beg < refs[cur].last_beg) {
+                bad_line(at, e, "positions decrease");
+                return SVX_OK;
+            }
+            refs[cur].last_beg = beg;
+            if (end > max_end) max_end = end;
+            recs.push_back({(uint32_t)cur, beg, end, voff(at), voff(next)});
+            at = next;
+        }
+        const bool csi = max_end > (1ll << 29);
+        const int min_shift = 14, depth = csi ? 6 : 5;
+        if (csi && max_end > (1ll << 32)) { if (err && err_cap) snprintf(err, err_cap, "a record ends beyond 2^32"); return SVX_E_INVALID; }
+        const uint32_t n_bins = (uint32_t)(((1u << (3 * depth + 3)) - 1) / 7), meta = n_bins + 1;
+        for (const Rec& r : recs) {
+            TbxRef& R = refs[r.ref];
+            if (R.n_rec == 0) R.first = r.vb;
+            R.last = r.ve;
+            R.n_rec++;
+            const uint32_t bin = reg2bin(r.beg, r.end, min_shift, depth);
+            if (R.bin_at.size() <= bin) R.bin_at.resize(bin + 1, -1);
+            if (R.bin_at[bin] < 0) { R.bin_at[bin] = (int64_t)R.bins.size(); R.bins.push_back({bin, {}}); }
+            std::vector<TbxChunk>& ch = R.bins[R.bin_at[bin]].second;
+            if (!ch.empty() && ch.back().end == r.vb) ch.back().end = r.ve;
+            else ch.push_back({r.vb, r.ve});
+            const uint64_t w0 = (uint64_t)r.beg >> min_shift, w1 = (uint64_t)(r.end - 1) >> min_shift;
+            if (R.ioff.size() <= w1) R.ioff.resize(w1 + 1, UINT64_MAX);
+            for (uint64_t w = w0; w <= w1; ++w)
+                if (R.ioff[w] == UINT64_MAX) R.ioff[w] = r.vb;
+        }
+        for (TbxRef& R : refs) {  // leading empty windows: the first record's offset; later ones: the window before
+            for (size_t w = 0; w < R.ioff.size(); ++w)
+                if (R.ioff[w] == UINT64_MAX) R.ioff[w] = w == 0 ? R.first : R.ioff[w - 1];
+        }
+        std::string names;
+        for (const TbxRef& R : refs) { names += R.name; names.push_back('\0'); }
+        std::string o;
+        auto tbx_conf = [&](std::string& x) {
+            put32(x, 2); put32(x, 1); put32(x, 2); put32(x, 0); put32(x, '#'); put32(x, 0);
+            put32(x, (uint32_t)names.size());
+            x += names;
+        };
+        if (csi) {
+            o.append("CSI\1", 4);
+            put32(o, (uint32_t)min_shift);
+            put32(o, (uint32_t)depth);
+            std::string aux;
+            tbx_conf(aux);
+            put32(o, (uint32_t)aux.size());
+            o += aux;
+        } else {
+            o.append("TBI\1", 4);
+            put32(o, (uint32_t)refs.size());
+            tbx_conf(o);
+        }
+        if (csi) put32(o, (uint32_t)refs.size());
+        for (const TbxRef& R : refs) {
+            put32(o, (uint32_t)R.bins.size() + 1u);
+            for (const auto& b : R.bins) {
+                put32(o, b.first);
+                if (csi) {  // loffset: the linear-index offset of the bin's first window (htslib's update_loff)
+                    int l = 0;
+                    uint32_t t = 0, bin = b.first;
+                    while (l < depth && bin >= t + (1u << 3 * l)) { t += 1u << 3 * l; ++l; }
+                    const uint64_t beg_w = (uint64_t)(bin - t) << (3 * (depth - l));
+                    put64(o, R.ioff[beg_w < R.ioff.size() ? beg_w : R.ioff.size() - 1]);
+                }
+                put32(o, (uint32_t)b.second.size());
+                for (const TbxChunk& c : b.second) { put64(o, c.beg); put64(o, c.end); }
+            }
+            put32(o, meta);
+            if (csi) put64(o, 0);
+            put32(o, 2);
+            put64(o, R.first); put64(o, R.last);
+            put64(o, R.n_rec); put64(o, 0);
+            if (!csi) {
+                put32(o, (uint32_t)R.ioff.size());
+                for (uint64_t v : R.ioff) put64(o, v);
+            }
+        }
+        put64(o, 0);  // n_no_coor
+        uint8_t* buf = (uint8_t*)malloc(o.size());
+        if (!buf) return SVX_E_NOMEM;
+        memcpy(buf, o.data(), o.size());
+        *index = buf;
+        *index_len = o.size();
+        *kind = csi ? 2 : 1;
+        return SVX_OK;
+    } catch (const std::bad_alloc&) {
+        return SVX_E_NOMEM;
+    } catch (...) {
+        return SVX_E_INVALID;
+    }
+}
