@@ -10,8 +10,10 @@ latency.  Multi-GPU: one process per GPU (torch.distributed / RCCL only for the 
 the max-over-ranks reduction; the data path has no collective — alignments shard by sample
 and contig), weak scaling: every rank processes its own cohort.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
-`cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what
+the headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.  `--full`
+adds the further regions and sustained steps, the `roofline` and `cpu_baseline` objects, the
+oracle check of the step's output and the legs outside the timed region.
 """
 import argparse
 import json
@@ -33,8 +35,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-steady", action="store_true", help="skip the 200 further steps behind the timed region "
-                    "(`sustained` in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too: four more timed regions and the sustained "
+                         "steps, the roofline, the oracle check of the step's output, the CPU baseline and the legs outside "
+                         "the timed region (the --no-* options below trim this); without it a run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--no-steady", action="store_true", help="--full: skip the 200 further steps behind the timed region "
+                    "(`sustained` in the line) and the four regions beside it")
     ap.add_argument("--prewarm-ms", type=float, default=0.0, help="diagnostic: keep the device busy with a torch fill loop "
                     "for this long right before the warm-up steps (is the slow start of the timed region the device's clocks?)")
     ap.add_argument("--step-trace", type=int, default=0, help="diagnostic: after the timed region leave the device idle "
@@ -43,8 +50,8 @@ def parse():
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic samples (replicated to --samples)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 5), help="BASELINE config: 2 (mean M run 4000) or 5 (400)")
     ap.add_argument("--min-sv-size", type=int, default=40)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: how long the CPU baseline runs")
     ap.add_argument("--layout", default="packed", choices=("packed", "soa"))
     ap.add_argument("--step", default="collect", choices=("collect", "split"),
                     help="collect (default): one step = svx_collect_batch_dev on the cohort, the product's own submission on one "
@@ -65,10 +72,10 @@ def parse():
     ap.add_argument("--settle-ms", type=float, default=300.0, help="host idle time in front of the warm-up steps (lets the "
                     "cgroup's CPU quota period roll over: see the comment at the timed region); 0 = none")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip latency_case / roofline_pair / roofline_editdist (N=1) and e2e / e2e_sharded (any N) — "
+                    help="--full: skip latency_case / roofline_pair / roofline_editdist (N=1) and e2e / e2e_sharded (any N) — "
                          "rank 0 only, all outside the timed region of `value`")
     ap.add_argument("--e2e-scale", type=float, default=1.0,
-                    help="BAM->VCF wall-clock legs (e2e, e2e_sharded): fraction of the GRCh38 contig lengths of the "
+                    help="--full: BAM->VCF wall-clock legs (e2e, e2e_sharded): fraction of the GRCh38 contig lengths of the "
                          "synthetic diploid sample written as real BAM+FASTA files (1.0 = 3.1 Gbp, the configuration the "
                          "metric is quoted on: ~1 min of generation on the GPU box); 0 skips the legs")
     ap.add_argument("--a3-after-dominant", type=int, default=0,
@@ -1038,9 +1045,10 @@ def main():
         dump_outputs(args.dump_outputs, collect_outputs(rcs[last]) if args.step == "collect" else
                      split_outputs(out_sets[last], d_raw, cap))
     # `value` is the region above — the FIRST `steps` steps behind the warm-up, as the contract asks.  Four more regions of
-    # the same length, bracketed the same way, give the spread of a 7-ms measurement (`value_median_of_5`).
+    # the same length, bracketed the same way, give the spread of a 7-ms measurement (`value_median_of_5`, --full).
+    more_regions = args.full and not args.no_steady
     repeats = [elapsed]
-    for _ in range(0 if args.no_steady else 4):
+    for _ in range(4 if more_regions else 0):
         barrier()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -1052,7 +1060,7 @@ def main():
     # host prepared the batch, and its clocks are still on their way up (the same 20 steps after 50 warm-up steps take
     # 0.31 ms each instead of 0.35).  Here: 200 further steps, bracketed the same way.
     steady = None
-    if not args.no_steady:
+    if more_regions:
         barrier()
         t1 = time.perf_counter()
         for _ in range(200):
@@ -1104,96 +1112,78 @@ def main():
                        host=socket.gethostname(), pid=os.getpid(), shares_device_0=bool(args.share_device))
     rank_fields = multi_rank_fields(gather_rank_records(dist, world, rank_record, grouped), args.backend, probe_sum, world, grouped)
 
-    # ---- roofline of the dominant kernel: HIP events on its launch stream around every launch of the step's own
-    # sequence (context 0; the event pair brackets the kernel itself).  The dominant kernel of the step is the streaming
-    # tile launch k_cigar_tiles<4096> — with --step collect the split-segment chain rides in the finish and dense
-    # launches behind it, so the chain's bytes count for the PATH figure, not for this kernel ----
-    torch.cuda.synchronize(dev)
-    op_bytes = 5 if args.layout == "soa" else 4  # packed u32 per op; SoA: a u8 op code next to the u32 length
-    algo_bytes = op_bytes * n_ops + 16 * n_aln + 17 * n_sig  # SURVEY.md §8(d), whole a1+a2 path
-    # what the tile workgroups themselves move of those: the op stream, aln_off, the slab records (16 B per
-    # signature) and one 16-B descriptor + one 4-B start index per tile; the 17-B final records are written by
-    # the finish kernel and only count for the path figure
-    n_tiles = (n_ops + 4095) // 4096
-    tile_bytes = op_bytes * n_ops + 8 * n_aln + 16 * n_sig + 20 * n_tiles
+    if args.full:
+        # ---- roofline of the dominant kernel: HIP events on its launch stream around every launch of the step's own
+        # sequence (context 0; the event pair brackets the kernel itself).  The dominant kernel of the step is the streaming
+        # tile launch k_cigar_tiles<4096> — with --step collect the split-segment chain rides in the finish and dense
+        # launches behind it, so the chain's bytes count for the PATH figure, not for this kernel ----
+        torch.cuda.synchronize(dev)
+        op_bytes = 5 if args.layout == "soa" else 4  # packed u32 per op; SoA: a u8 op code next to the u32 length
+        algo_bytes = op_bytes * n_ops + 16 * n_aln + 17 * n_sig  # SURVEY.md §8(d), whole a1+a2 path
+        # what the tile workgroups themselves move of those: the op stream, aln_off, the slab records (16 B per
+        # signature) and one 16-B descriptor + one 4-B start index per tile; the 17-B final records are written by
+        # the finish kernel and only count for the path figure
+        n_tiles = (n_ops + 4095) // 4096
+        tile_bytes = op_bytes * n_ops + 8 * n_aln + 16 * n_sig + 20 * n_tiles
 
-    def timed(fn):
-        ctx.set_timing(True)
-        k_ms, p_ms = [], []
-        for _ in range(max(5, min(20, args.steps))):
-            fn()
-            ctx.sync()
-            tot_ms, dom_ms = ctx.last_kernel_ms()
-            k_ms.append(dom_ms)
-            p_ms.append(tot_ms)
-        ctx.set_timing(False)
-        return float(np.mean(k_ms)) * 1e-3, float(np.mean(p_ms)) * 1e-3
+        def timed(fn):
+            ctx.set_timing(True)
+            k_ms, p_ms = [], []
+            for _ in range(max(5, min(20, args.steps))):
+                fn()
+                ctx.sync()
+                tot_ms, dom_ms = ctx.last_kernel_ms()
+                k_ms.append(dom_ms)
+                p_ms.append(tot_ms)
+            ctx.set_timing(False)
+            return float(np.mean(k_ms)) * 1e-3, float(np.mean(p_ms)) * 1e-3
 
-    def a1a2_only():
-        ctx.cigar_extract_dev(d_cig_ptr, n_ops, d_off_ptr, n_aln, d_rs_ptr, args.min_sv_size, outs, cap, d_n_ptr, d_op=d_op_ptr)
-    tiles_k, tiles_p = timed(a1a2_only)
-    chain_bytes = 0
-    if args.step == "collect":
-        # bytes of the chain's stage A inside the same launch: the CIGARs of the segments' alignments (4 B per op), per
-        # segment its table row in (seg_src, two offsets, tid, pos, rev, qend: 33 B), the 24-B row and the read length
-        # out and in again, the 32-B raw record out; per read two offsets and its length
-        seg_ops = int((batch["aln_off"][1:] - batch["aln_off"][:-1])[case["seg_src"][case["seg_src"] < n_aln].astype(np.int64)].sum()) + \
-            int(len(case["extra_cigar"]))
-        chain_bytes = 4 * seg_ops + (33 + 2 * 28 + 32) * n_segs + 12 * n_reads
-        k_avg, p_avg = timed(rc0.step)
-        kernel_bytes = tile_bytes
-    else:
-        k_avg, p_avg, kernel_bytes = tiles_k, tiles_p, tile_bytes
-    achieved = kernel_bytes / k_avg / 1e9
-
-    # second denominator: the read-only nontemporal stream this box sustains over the very buffer
-    # the kernel reads, measured in this run (svx_hbm_read_probe_dev) — <= the spec peak by construction
-    try:
-        read_gbs = ctx.hbm_read_probe(d_cig_ptr, (op_bytes - (1 if args.layout == "soa" else 0)) * n_ops // 16 * 16, 5)
-    except Exception:
-        read_gbs = None
-
-    # correctness spot-check of what the timed loop produced (oracle = checker only)
-    if rank == 0 and not os.environ.get("SVX_BENCH_NOCHECK"):  # (ablation builds of tools/ skip the check)
+        def a1a2_only():
+            ctx.cigar_extract_dev(d_cig_ptr, n_ops, d_off_ptr, n_aln, d_rs_ptr, args.min_sv_size, outs, cap, d_n_ptr, d_op=d_op_ptr)
+        tiles_k, tiles_p = timed(a1a2_only)
+        chain_bytes = 0
         if args.step == "collect":
-            rc0.step()
-            ctx.sync()
-            ok = rc0.check(n_aln_checked=2000, n_reads_checked=2000)
+            # bytes of the chain's stage A inside the same launch: the CIGARs of the segments' alignments (4 B per op), per
+            # segment its table row in (seg_src, two offsets, tid, pos, rev, qend: 33 B), the 24-B row and the read length
+            # out and in again, the 32-B raw record out; per read two offsets and its length
+            seg_ops = int((batch["aln_off"][1:] - batch["aln_off"][:-1])[case["seg_src"][case["seg_src"] < n_aln].astype(np.int64)].sum()) + \
+                int(len(case["extra_cigar"]))
+            chain_bytes = 4 * seg_ops + (33 + 2 * 28 + 32) * n_segs + 12 * n_reads
+            k_avg, p_avg = timed(rc0.step)
+            kernel_bytes = tile_bytes
         else:
-            from oracle import orc
-            a_chk = min(n_aln, 2000)
-            exp = orc.cigar_extract(cig_np[:int(batch["aln_off"][a_chk])], batch["aln_off"][:a_chk + 1],
-                                    batch["ref_start"][:a_chk], args.min_sv_size)
-            k = len(exp["aln"])
-            o_aln, o_ref, o_read, o_len, o_type = out_sets[0][:5]
-            ok = (np.array_equal(o_ref[:k].cpu().numpy().view(np.uint32), exp["ref_pos"]) and
-                  np.array_equal(o_read[:k].cpu().numpy().view(np.uint32), exp["read_pos"]) and
-                  np.array_equal(o_aln[:k].cpu().numpy().view(np.uint32), exp["aln"]) and
-                  np.array_equal(o_len[:k].cpu().numpy().view(np.uint32), exp["len"]) and
-                  np.array_equal(o_type[:k].cpu().numpy(), exp["type"]))
-        if not ok:
-            raise SystemExit("bench output differs from the oracle on the checked prefix")
+            k_avg, p_avg, kernel_bytes = tiles_k, tiles_p, tile_bytes
+        achieved = kernel_bytes / k_avg / 1e9
+
+        # second denominator: the read-only nontemporal stream this box sustains over the very buffer
+        # the kernel reads, measured in this run (svx_hbm_read_probe_dev) — <= the spec peak by construction
+        try:
+            read_gbs = ctx.hbm_read_probe(d_cig_ptr, (op_bytes - (1 if args.layout == "soa" else 0)) * n_ops // 16 * 16, 5)
+        except Exception:
+            read_gbs = None
+
+        # correctness spot-check of what the timed loop produced (oracle = checker only)
+        if rank == 0 and not os.environ.get("SVX_BENCH_NOCHECK"):  # (ablation builds of tools/ skip the check)
+            if args.step == "collect":
+                rc0.step()
+                ctx.sync()
+                ok = rc0.check(n_aln_checked=2000, n_reads_checked=2000)
+            else:
+                from oracle import orc
+                a_chk = min(n_aln, 2000)
+                exp = orc.cigar_extract(cig_np[:int(batch["aln_off"][a_chk])], batch["aln_off"][:a_chk + 1],
+                                        batch["ref_start"][:a_chk], args.min_sv_size)
+                k = len(exp["aln"])
+                o_aln, o_ref, o_read, o_len, o_type = out_sets[0][:5]
+                ok = (np.array_equal(o_ref[:k].cpu().numpy().view(np.uint32), exp["ref_pos"]) and
+                      np.array_equal(o_read[:k].cpu().numpy().view(np.uint32), exp["read_pos"]) and
+                      np.array_equal(o_aln[:k].cpu().numpy().view(np.uint32), exp["aln"]) and
+                      np.array_equal(o_len[:k].cpu().numpy().view(np.uint32), exp["len"]) and
+                      np.array_equal(o_type[:k].cpu().numpy(), exp["type"]))
+            if not ok:
+                raise SystemExit("bench output differs from the oracle on the checked prefix")
 
     if rank == 0:
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        wl_key = "config%d_x%d_%s" % (args.config, args.samples, args.layout)
-        if os.path.exists(tpath):
-            try:
-                entry = json.load(open(tpath)).get(wl_key, {})
-                traffic = entry.get("hbm_bytes_per_launch")
-                # the committed counters belong to ONE workload: the bytes this run's launch counts must be the ones the
-                # counter passes' launch counted (same ops, alignments, signatures, tiles), else no figure at all
-                counted = entry.get("counted_bytes_per_launch")
-                if traffic is not None and counted is not None and abs(kernel_bytes - counted) > 0.002 * counted:
-                    traffic = None
-                if traffic is not None:
-                    # not a property of THIS run: PMC counters need their own rocprofv3 passes (separate --pmc runs,
-                    # MI355X_MICROARCH.md); the figure is the committed one of the same workload and kernel
-                    traffic_source = "%s (%s; collected by the builder with rocprofv3 --pmc, not in this run)" % (
-                        entry.get("source"), entry.get("method", "").split(";")[0])
-            except Exception:
-                traffic = None
         res = {
             "metric": "CIGAR ops/sec (SV-signature extraction, human genome-genome alignment)",
             "value": total_ops * args.steps / elapsed,
@@ -1202,13 +1192,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "value_median_of_5": (float(np.median([total_ops * args.steps / e for e in repeats])) if len(repeats) == 5 else None),
-            "all_regions_ms_per_step": [e / args.steps * 1e3 for e in repeats],  # the first is `value`'s
             "host_throttled_ms_in_timed_region": host_throttled_ms,  # (cgroup cpu.stat; rank 0's group; None: not exposed)
-            "sustained": None if steady is None else dict(steady, value=total_ops * 200 / (steady["ms_per_step"] * 200 * 1e-3),
-                                                          note="200 further steps behind the timed region, bracketed the same "
-                                                               "way (barrier + synchronize, max over ranks): the rate of a device "
-                                                               "whose clocks have come up; `value` is the timed region as asked"),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1229,30 +1213,58 @@ def main():
                         % ("; two contexts alternate between steps" if args.pipeline else ""),
                 "parallelism": "sample/contig shards x%d, no data-path collective" % world,
             },
-            "roofline": {
-                "bound": "hbm", "kernel": "k_cigar_tiles<false, 4096, 0>",
-                "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                "kernel_bytes_per_launch": kernel_bytes, "algorithmic_bytes_per_launch": algo_bytes + chain_bytes,
-                "chain_bytes_in_the_path": chain_bytes,  # the split-segment chain's stage A (in the finish launch): the segments'
-                # CIGARs read again + rows / raw records / table entries
-                "kernel_ms": k_avg * 1e3,
-                "path_ms": p_avg * 1e3, "path_achieved": (algo_bytes + chain_bytes) / p_avg / 1e9,
-                "path_frac": (algo_bytes + chain_bytes) / p_avg / 1e9 / HBM_PEAK_GBS,
-                # ... and the same bytes over the step as `value` times it (launch gaps and the device's ramp included)
-                "step_frac": (algo_bytes + chain_bytes) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
-                "a1a2_only": {"kernel": "k_cigar_tiles<false, 4096, 0>", "note": "svx_cigar_extract_dev alone (no chimeric reads in the "
-                              "submission: no chain in the finish and dense launches): the call rounds 1-3 timed", "kernel_ms": tiles_k * 1e3,
-                              "kernel_bytes_per_launch": tile_bytes,
-                              "achieved": tile_bytes / tiles_k / 1e9, "frac": tile_bytes / tiles_k / 1e9 / HBM_PEAK_GBS,
-                              "path_ms": tiles_p * 1e3, "path_frac": algo_bytes / tiles_p / 1e9 / HBM_PEAK_GBS},
-                "read_ceiling": read_gbs, "frac_of_read_ceiling": (achieved / read_gbs) if read_gbs else None,
-                "read_ceiling_note": "read-only nontemporal stream over the same resident CIGAR buffer, measured in this run "
-                                     "(svx_hbm_read_probe_dev)",
-            },
         }
+        if args.full:
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            wl_key = "config%d_x%d_%s" % (args.config, args.samples, args.layout)
+            if os.path.exists(tpath):
+                try:
+                    entry = json.load(open(tpath)).get(wl_key, {})
+                    traffic = entry.get("hbm_bytes_per_launch")
+                    # the committed counters belong to ONE workload: the bytes this run's launch counts must be the ones the
+                    # counter passes' launch counted (same ops, alignments, signatures, tiles), else no figure at all
+                    counted = entry.get("counted_bytes_per_launch")
+                    if traffic is not None and counted is not None and abs(kernel_bytes - counted) > 0.002 * counted:
+                        traffic = None
+                    if traffic is not None:
+                        # not a property of THIS run: PMC counters need rocprofv3 --pmc passes of their own; the figure
+                        # is the committed one of the same workload and kernel
+                        traffic_source = "%s (%s; collected by the builder with rocprofv3 --pmc, not in this run)" % (
+                            entry.get("source"), entry.get("method", "").split(";")[0])
+                except Exception:
+                    traffic = None
+            res.update({
+                "value_median_of_5": (float(np.median([total_ops * args.steps / e for e in repeats])) if len(repeats) == 5 else None),
+                "all_regions_ms_per_step": [e / args.steps * 1e3 for e in repeats],  # the first is `value`'s
+                "sustained": None if steady is None else dict(steady, value=total_ops * 200 / (steady["ms_per_step"] * 200 * 1e-3),
+                                                              note="200 further steps behind the timed region, bracketed the same "
+                                                                   "way (barrier + synchronize, max over ranks): the rate of a device "
+                                                                   "whose clocks have come up; `value` is the timed region as asked"),
+                "roofline": {
+                    "bound": "hbm", "kernel": "k_cigar_tiles<false, 4096, 0>",
+                    "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel_bytes_per_launch": kernel_bytes, "algorithmic_bytes_per_launch": algo_bytes + chain_bytes,
+                    "chain_bytes_in_the_path": chain_bytes,  # the split-segment chain's stage A (in the finish launch): the segments'
+                    # CIGARs read again + rows / raw records / table entries
+                    "kernel_ms": k_avg * 1e3,
+                    "path_ms": p_avg * 1e3, "path_achieved": (algo_bytes + chain_bytes) / p_avg / 1e9,
+                    "path_frac": (algo_bytes + chain_bytes) / p_avg / 1e9 / HBM_PEAK_GBS,
+                    # ... and the same bytes over the step as `value` times it (launch gaps and the device's ramp included)
+                    "step_frac": (algo_bytes + chain_bytes) / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
+                    "a1a2_only": {"kernel": "k_cigar_tiles<false, 4096, 0>", "note": "svx_cigar_extract_dev alone (no chimeric reads in the "
+                                  "submission: no chain in the finish and dense launches): the call rounds 1-3 timed", "kernel_ms": tiles_k * 1e3,
+                                  "kernel_bytes_per_launch": tile_bytes,
+                                  "achieved": tile_bytes / tiles_k / 1e9, "frac": tile_bytes / tiles_k / 1e9 / HBM_PEAK_GBS,
+                                  "path_ms": tiles_p * 1e3, "path_frac": algo_bytes / tiles_p / 1e9 / HBM_PEAK_GBS},
+                    "read_ceiling": read_gbs, "frac_of_read_ceiling": (achieved / read_gbs) if read_gbs else None,
+                    "read_ceiling_note": "read-only nontemporal stream over the same resident CIGAR buffer, measured in this run "
+                                         "(svx_hbm_read_probe_dev)",
+                },
+            })
         res.update(rank_fields)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             res["cpu_baseline"] = cpu_baseline(batch, args)
             res["speedup_vs_cpu_port"] = res["value"] / res["cpu_baseline"]["value"]
     # ---- legs outside the timed region (rank 0).  Several ranks: the process group is closed first and the other
@@ -1269,7 +1281,7 @@ def main():
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK"):
             os.environ.pop(k, None)
     if rank == 0:
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             if args.step == "collect":  # the cohort is not needed any more
                 for r_ in rcs:
                     r_.free()
@@ -1307,13 +1319,15 @@ def main():
             best = max((r for r in coh if isinstance(r, dict) and r.get("samples_per_s")), key=lambda r: r["samples"], default=None)
             if best:
                 res["cpu_seconds_per_sample"], res["cpu_quota_cpus"] = best.get("cpu_seconds_per_sample"), best.get("cpu_quota_cpus")
-        if "cpu_quota_cpus" not in res:
+        if args.full and "cpu_quota_cpus" not in res:
             from tools import e2e_bench
             res["cpu_quota_cpus"] = e2e_bench.cpu_quota()
             sam = res.get("e2e_samples", {}).get("runs") if isinstance(res.get("e2e_samples"), dict) else None
             if sam and isinstance(sam[-1], dict) and sam[-1].get("cpu_seconds_all_processes"):
                 res["cpu_seconds_per_sample"] = sam[-1]["cpu_seconds_all_processes"] / sam[-1]["processes"]
-        res["summary"] = summary_of(res)  # the LAST key: the driver keeps the line's last 2 000 bytes
+        # the LAST key: the driver keeps the line's last 2 000 bytes (a plain run's line is short, but at N ranks its rank
+        # records may push the headline out of that tail)
+        res["summary"] = summary_of(res) if args.full else {"value": res["value"], "ms_per_step": res["ms_per_step"]}
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(res) + "\n").encode())
 

@@ -4,7 +4,7 @@ reps=$1; args=$2; shift 2
 mkdir -p gpurun_out; rm -f gpurun_out/abmed_*.txt
 for r in $(seq $reps); do
   for lib in "$@"; do
-    SVX_LIB=$PWD/$lib timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline $args 2>/dev/null | python -c "
+    SVX_LIB=$PWD/$lib timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $args 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); rf=r['roofline']
 print(rf['kernel_ms'], rf['path_ms'], r['ms_per_step'])" >> gpurun_out/abmed_$(basename $lib .so).txt

@@ -3,7 +3,7 @@
 lib=$1; shift
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/ks_$(basename $lib .so); rm -rf $out; mkdir -p $out
-SVX_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o s -- python3 bench.py --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.txt
+SVX_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o s -- python3 bench.py --full --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.txt
 python3 - $out <<'PY'
 import csv, sys
 for r in csv.DictReader(open(sys.argv[1] + "/s_kernel_stats.csv")):

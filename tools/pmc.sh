@@ -13,7 +13,7 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_
   if [ -n "$PMC_CMD" ]; then
     rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out" -o pass$i -- python3 $PMC_CMD > /dev/null 2>> "$out/err.txt"
   else
-    rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out" -o pass$i -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras "$@" > /dev/null 2>> "$out/err.txt"
+    rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out" -o pass$i -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras "$@" > /dev/null 2>> "$out/err.txt"
   fi
 done
 python3 - "$out" <<'PY'

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 for lib in "$@"; do
   out=gpurun_out/seg_$(basename $lib .so); rm -rf $out; mkdir -p $out
-  SVX_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o s -- python3 bench.py --no-cpu-baseline --no-extras --steps 30 > /dev/null 2> $out/err.txt
+  SVX_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o s -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 30 > /dev/null 2> $out/err.txt
   echo "== $lib"; python3 - $out <<'PY'
 import csv, sys, glob
 f = glob.glob(sys.argv[1] + "/**/s_kernel_stats.csv", recursive=True)[0]
