@@ -196,6 +196,22 @@ SYMBOLS = {
     "svx_bam_load": (C.c_int, [_P, _P, C.c_int32]),
     "svx_bam_get_columns": (C.c_int, [_P, _P]),
     "svx_bam_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
+    # native SAM ingest and the CIGAR-text parsers (include/svx_sam.h)
+    "svx_sam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "svx_sam_close": (None, [_P]),
+    "svx_sam_last_error": (C.c_char_p, [_P]),
+    "svx_sam_header": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "svx_sam_reference": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "svx_sam_set_pinned_device": (C.c_int, [_P, C.c_int]),
+    "svx_sam_set_device_parse": (C.c_int, [_P, C.c_int]),
+    "svx_sam_parsed_on_device": (C.c_int, [_P]),
+    "svx_sam_load": (C.c_int, [_P, _P, C.c_int32]),
+    "svx_sam_get_columns": (C.c_int, [_P, _P]),
+    "svx_sam_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
+    "svx_sam_device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
+    "svx_sam_device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "svx_cigar_text_parse": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_int]),
+    "svx_cigar_text_parse_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     "svx_inflate_raw": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint64)]),
     "svx_inflate_raw_pair": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                        _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
@@ -378,6 +394,24 @@ class Context:
         ms = C.c_float()
         self._check(self.lib.svx_hbm_read_probe_dev(self.h, d_ptr, int(nbytes), int(reps), C.byref(ms)))
         return nbytes / (ms.value * 1e-3) / 1e9
+
+    def cigar_text_parse(self, text, rec_off):
+        """CIGAR strings back to back (`text`: bytes-like, `rec_off`: n + 1 offsets) -> dict(words, cigar_off, ref_len,
+        status) by svx_cigar_text_parse_dev's kernels (include/svx_sam.h; cigar_text_parse_host is the same on threads)."""
+        text, rec_off, n, cap = _cigar_text_args(text, rec_off)
+        d_text, d_off = self.dev_array(nbytes=max(1, len(text))), self.dev_array(rec_off)
+        if len(text):
+            self._check(self.lib.svx_dev_upload(self.h, d_text.ptr, text.ctypes.data, len(text)))
+        d_words, d_coff = self.dev_array(nbytes=4 * max(1, cap)), self.dev_array(nbytes=8 * (n + 1))
+        d_rl, d_st = self.dev_array(nbytes=4 * max(1, n)), self.dev_array(nbytes=4 * max(1, n))
+        self._check(self.lib.svx_cigar_text_parse_dev(self.h, d_text.ptr, len(text), d_off.ptr, n, d_words.ptr, cap, d_coff.ptr,
+                                                      d_rl.ptr, d_st.ptr))
+        coff = d_coff.download(np.uint64)
+        out = {"words": d_words.download(np.uint32, int(coff[-1])), "cigar_off": coff, "ref_len": d_rl.download(np.int32, n),
+               "status": d_st.download(np.uint32, n)}
+        for d in (d_text, d_off, d_words, d_coff, d_rl, d_st):
+            d.free()
+        return out
 
     def last_kernel_ms(self):
         t, d = C.c_float(), C.c_float()
@@ -657,6 +691,26 @@ class Context:
             self._check(self.lib.svx_linkage_cut_batch(self.h, _ptr(dist), _ptr(n_members), len(n_members),
                                                        float(cutoff), _ptr(labels)))
         return labels
+
+
+def _cigar_text_args(text, rec_off):
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if len(rec_off) < 1 or int(rec_off[0]) != 0 or int(rec_off[-1]) != len(text):
+        raise ValueError("rec_off must run from 0 to len(text)")
+    return text, rec_off, len(rec_off) - 1, len(text) // 2 + 1
+
+
+def cigar_text_parse_host(text, rec_off, threads=1):
+    """svx_cigar_text_parse (include/svx_sam.h) on `threads` host threads: dict(words, cigar_off, ref_len, status)."""
+    text, rec_off, n, cap = _cigar_text_args(text, rec_off)
+    words, coff = np.empty(cap, np.uint32), np.zeros(n + 1, np.uint64)
+    ref_len, status = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.uint32)
+    rc = load().svx_cigar_text_parse(text.ctypes.data if len(text) else None, len(text), rec_off.ctypes.data, n, words.ctypes.data,
+                                     cap, coff.ctypes.data, ref_len.ctypes.data, status.ctypes.data, int(threads))
+    if rc != 0:
+        raise SvxError(rc, "svx_cigar_text_parse")
+    return {"words": words[:int(coff[-1])].copy(), "cigar_off": coff, "ref_len": ref_len[:n], "status": status[:n]}
 
 
 def segment_rows(st, seg_tid, seg_pos, seg_rev, seg_qend, read_off):

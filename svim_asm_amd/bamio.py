@@ -582,6 +582,44 @@ def _view(addr, n, dtype):
     return np.frombuffer(buf, dtype=dtype, count=n)
 
 
+# Who turns a SAM's CIGAR strings into words when the reader has a device (svx_sam_set_device_parse, include/svx_sam.h):
+# SVX_SAM_DEVICE=1|0 decides, else this constant — set from the measurement in DESIGN.md §3.11, not from expectation.
+DEVICE_DEFAULT = True
+
+
+def sam_device_parse():
+    env = os.environ.get("SVX_SAM_DEVICE")
+    if env in ("0", "1"):
+        return env == "1"
+    return DEVICE_DEFAULT
+
+
+def is_sam(path):
+    """True when `path` takes the SAM reader: a readable file whose first bytes are not the gzip magic (BAM is BGZF;
+    anything gzip keeps to the BAM reader and its messages)."""
+    try:
+        with open(path, "rb") as f:
+            return f.read(2) != b"\x1f\x8b"
+    except OSError:
+        return False
+
+
+class _SamApi(object):
+    """The svx_sam_* entry points under the names AlignmentFile calls on a BAM handle; what only a BGZF file has (index,
+    CRC check, the device's share of the inflate work) is answered here."""
+
+    def __init__(self, lib):
+        for name in ("open", "close", "last_error", "header", "reference", "set_pinned_device", "load", "get_columns",
+                     "seq_slices", "device_pool", "device_pool_wait"):
+            setattr(self, "svx_bam_" + name, getattr(lib, "svx_sam_" + name))
+        self.svx_sam_set_device_parse = lib.svx_sam_set_device_parse
+        self.svx_sam_parsed_on_device = lib.svx_sam_parsed_on_device
+        for name in ("set_verify", "set_device_inflate", "set_device_inflate_min", "set_device_inflate_wait",
+                     "set_defer_verify", "verify_pending", "pending_members", "device_members"):
+            setattr(self, "svx_bam_" + name, lambda *a: 0)
+        self.svx_bam_index_state = lambda h: 0
+
+
 class AlignmentFile(object):
     """Coordinate-sorted BAM opened for per-contig streaming (pysam.AlignmentFile surface the
     reference uses).  Records are indexed column-wise by the native reader
@@ -592,18 +630,23 @@ class AlignmentFile(object):
     (kept as the differential reference of the native one; also via SVX_BAM_READER=python).
     verify (default True, or what SVX_BAM_VERIFY says): every touched BGZF member is inflated completely and its CRC32
     checked (what htslib does under the reference); verify=False stops at the last byte needed and checks a member
-    only when it happens to be inflated to its end (svx_bam_set_verify, include/svx_bam.h)."""
+    only when it happens to be inflated to its end (svx_bam_set_verify, include/svx_bam.h).
+    An uncompressed SAM (first bytes not gzip's) is read by the native SAM reader (include/svx_sam.h) whatever its record
+    order: the records are ordered in memory, `is_sam` is True, check_index() has nothing to ask for."""
 
     def __init__(self, path, mode="rb", threads=None, reader=None, device=None, verify=None):
         self.filename = path
         self._reader = reader or os.environ.get("SVX_BAM_READER", "native")
+        self.is_sam = is_sam(path)
+        if self.is_sam:
+            self._reader = "native"  # (the pure-Python walker reads BGZF only)
         self._loaded = None   # None: nothing; "all" or a tuple of tids
         self._h = None
         self._z = None
         self._pin_device = device
         if self._reader == "native":
             from svim_asm_amd import _lib
-            self._lib = lib = _lib.load()
+            self._lib = lib = _SamApi(_lib.load()) if self.is_sam else _lib.load()
             h, err = C.c_void_p(), C.create_string_buffer(512)
             rc = lib.svx_bam_open(os.fsencode(path), int(threads or 0), C.byref(h), err, len(err))
             if rc != 0:
@@ -723,6 +766,8 @@ class AlignmentFile(object):
             self._lib.svx_bam_set_device_inflate_min(self._h, int(self.device_inflate_min_members))
             self._lib.svx_bam_set_device_inflate_wait(self._h, int(self.device_inflate_wait_ms))
             self._lib.svx_bam_set_defer_verify(self._h, 1 if self.defer_verify else 0)
+            if self.is_sam:
+                self._lib.svx_sam_set_device_parse(self._h, 1 if sam_device_parse() else 0)
             if tids is None:
                 rc = self._lib.svx_bam_load(self._h, None, 0)
             else:
@@ -943,7 +988,14 @@ class AlignmentFile(object):
                 c["pos"][idx].astype(np.int32), c["tid"][idx].astype(np.int32))
 
     # ---- pysam-compatible surface
+    @property
+    def parsed_on_device(self):
+        """SAM input: whether the loaded CIGAR words were written by the device's kernels (False: by the threads)."""
+        return bool(self.is_sam and self._h is not None and self._lib.svx_sam_parsed_on_device(self._h))
+
     def check_index(self):
+        if self.is_sam:
+            return True  # (records are ordered in memory: there is nothing to index)
         if self.index_state() == 0:
             raise ValueError("mapping information not recorded in index or index not available")
         return True

@@ -62,6 +62,11 @@ def _open(path, which, options, opened=None):
     Returns the alignment file, or None after logging the error."""
     the = {"": "Input", "first": "The first input", "second": "The second input"}[which]
     aln_file = opened() if opened is not None else _open_file(path, options)
+    if getattr(aln_file, "is_sam", False):
+        # text input: whatever order minimap2 wrote, the reader presents the records by contig and coordinate
+        logging.info("{0} file is an uncompressed SAM: its records are ordered in memory (no sorted file and no index "
+                     "needed).".format(the))
+        return aln_file
     try:
         if aln_file.header["HD"]["SO"] != "coordinate":
             logging.error("{0} BAM file needs to be coordinate-sorted. Exiting..".format(the))
