@@ -40,6 +40,21 @@ int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, const int64_t
                           uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads);
 
 /*
+ * svx_fasta_fetch_batch with a direction per window and, when asked, the alphabet of a BAM record's SEQ: window i holds
+ * bases [start[i], min(end[i], length)) of sequence ref[i]; with reverse[i] != 0 (reverse == NULL: none) they are written
+ * as their REVERSE COMPLEMENT — output base k is the complement of source base end - 1 - k.  Complement: A<->T, C<->G,
+ * M<->K, R<->Y, V<->B, H<->D, in upper and in lower case; S, W, N, `=` and every other byte stay.  Then, with bam_alphabet
+ * != 0, every byte (of a reversed window or not) goes through the mapping of a BAM round trip — 4-bit code and back: lower
+ * case -> upper, anything outside =ACMGRSVTWYHKDBN -> N — as svx_bam_seq_slices and svx_sam_seq_slices write it; with
+ * bam_alphabet == 0 bytes keep their case.  This is how a query assembly serves the SEQ of an alignment that names only a
+ * span and a strand (svx_paf.h).  Same arguments, checks and back ends as svx_fasta_fetch_batch: a plain file on the host
+ * threads, a bgzip-compressed one on the threads or on the device (svx_fasta_set_device) — the same bytes either way.
+ */
+int svx_fasta_fetch_oriented(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end,
+                             const uint8_t* reverse, uint32_t n, int bam_alphabet, const uint64_t* out_off, uint8_t* out,
+                             int n_threads);
+
+/*
  * A bgzip-compressed FASTA (htslib faidx semantics): the .fai columns count UNCOMPRESSED bytes, and
  * gzi_coff / gzi_uoff[n_gzi] are the `<path>.gzi` pairs (compressed offset of a member, uncompressed offset of its
  * first byte; (0, 0) implicit, a final entry at the end of the data allowed).  At open the whole member chain is

@@ -70,6 +70,9 @@ def parse_arguments(program_version, arguments=None):
     haploid.add_argument("working_dir", type=os.path.abspath, help="Working and output directory (created if missing)")
     haploid.add_argument("bam_file", type=str, help="Coordinate-sorted and indexed BAM file of the query assembly")
     haploid.add_argument("genome", type=str, help="Reference genome FASTA (indexed with .fai)")
+    haploid.add_argument("--query", type=str, default=None, metavar="ASSEMBLY_FASTA",
+                         help="The input is minimap2's PAF (written with -c: cg:Z: CIGARs) and this is the query assembly it "
+                              "was aligned from (FASTA with .fai; bgzip-compressed with .gzi too): the bases are read from it")
 
     diploid = subparsers.add_parser("diploid", help="Detect SVs from the alignment of a diploid query assembly "
                                                     "(two haplotype BAMs) to a reference assembly")
@@ -77,6 +80,10 @@ def parse_arguments(program_version, arguments=None):
     diploid.add_argument("bam_file1", type=str, help="Coordinate-sorted and indexed BAM file of haplotype 1")
     diploid.add_argument("bam_file2", type=str, help="Coordinate-sorted and indexed BAM file of haplotype 2")
     diploid.add_argument("genome", type=str, help="Reference genome FASTA (indexed with .fai)")
+    for k in ("1", "2"):
+        diploid.add_argument("--query" + k, type=str, default=None, metavar="ASSEMBLY_FASTA",
+                             help="Input {0} is minimap2's PAF (written with -c: cg:Z: CIGARs) and this is the assembly of "
+                                  "haplotype {0} it was aligned from (FASTA with .fai; bgzip-compressed with .gzi too)".format(k))
 
     for sub in (haploid, diploid):
         sub.add_argument("--verbose", action="store_true", help="Enable more verbose logging")

@@ -210,6 +210,21 @@ SYMBOLS = {
     "svx_sam_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
     "svx_sam_device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
     "svx_sam_device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    # native PAF ingest (include/svx_paf.h)
+    "svx_paf_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "svx_paf_close": (None, [_P]),
+    "svx_paf_last_error": (C.c_char_p, [_P]),
+    "svx_paf_header": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "svx_paf_reference": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "svx_paf_set_pinned_device": (C.c_int, [_P, C.c_int]),
+    "svx_paf_set_device_parse": (C.c_int, [_P, C.c_int]),
+    "svx_paf_parsed_on_device": (C.c_int, [_P]),
+    "svx_paf_load": (C.c_int, [_P, _P, C.c_int32]),
+    "svx_paf_get_columns": (C.c_int, [_P, _P]),
+    "svx_paf_set_query": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "svx_paf_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
+    "svx_paf_device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
+    "svx_paf_device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "svx_cigar_text_parse": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_int]),
     "svx_cigar_text_parse_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     "svx_inflate_raw": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -219,6 +234,7 @@ SYMBOLS = {
     "svx_fasta_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, _P, _P, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_fasta_close": (None, [_P]),
     "svx_fasta_fetch_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_int]),
+    "svx_fasta_fetch_oriented": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_int]),
     "svx_fasta_open_bgzf": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(_P), C.c_char_p,
                                       C.c_size_t]),
     "svx_fasta_is_bgzf": (C.c_int, [_P]),

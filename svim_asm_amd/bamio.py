@@ -620,6 +620,47 @@ class _SamApi(object):
         self.svx_bam_index_state = lambda h: 0
 
 
+def read_fai_dictionary(fasta_path):
+    """(names, lengths) of `fasta_path`.fai in file order: the reference dictionary a PAF is read against."""
+    names, lengths = [], []
+    with open(fasta_path + ".fai") as fh:
+        for line in fh:
+            f = line.rstrip("\n").split("\t")
+            if len(f) >= 2:
+                names.append(f[0])
+                lengths.append(int(f[1]))
+    return names, lengths
+
+
+class _PafApi(_SamApi):
+    """The svx_paf_* entry points (include/svx_paf.h) under the names AlignmentFile calls on a BAM handle.  The reference
+    dictionary goes in at open; the bases come from the query assembly the handle is bound to (svx_paf_set_query)."""
+
+    def __init__(self, lib, dictionary):
+        for name in ("close", "last_error", "header", "reference", "set_pinned_device", "load", "get_columns", "seq_slices",
+                     "device_pool", "device_pool_wait"):
+            setattr(self, "svx_bam_" + name, getattr(lib, "svx_paf_" + name))
+        self.svx_sam_set_device_parse = lib.svx_paf_set_device_parse
+        self.svx_sam_parsed_on_device = lib.svx_paf_parsed_on_device
+        for name in ("set_verify", "set_device_inflate", "set_device_inflate_min", "set_device_inflate_wait",
+                     "set_defer_verify", "verify_pending", "pending_members", "device_members"):
+            setattr(self, "svx_bam_" + name, lambda *a: 0)
+        self.svx_bam_index_state = lambda h: 0
+        self._lib, self._dictionary = lib, dictionary
+
+    def svx_bam_open(self, path, threads, out, err, err_cap):
+        names, lengths = self._dictionary
+        arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        lens = np.asarray(lengths, dtype=np.int32)
+        return self._lib.svx_paf_open(path, len(names), arr, lens.ctypes.data, threads, out, err, err_cap)
+
+    def bind_query(self, h, fasta):
+        lib, fh = fasta._handle()
+        arr = (C.c_char_p * max(1, len(fasta.references)))(*[n.encode() for n in fasta.references])
+        lens = np.asarray(fasta.lengths, dtype=np.int64)
+        return self._lib.svx_paf_set_query(h, fh, len(fasta.references), arr, lens.ctypes.data)
+
+
 class AlignmentFile(object):
     """Coordinate-sorted BAM opened for per-contig streaming (pysam.AlignmentFile surface the
     reference uses).  Records are indexed column-wise by the native reader
@@ -632,12 +673,23 @@ class AlignmentFile(object):
     checked (what htslib does under the reference); verify=False stops at the last byte needed and checks a member
     only when it happens to be inflated to its end (svx_bam_set_verify, include/svx_bam.h).
     An uncompressed SAM (first bytes not gzip's) is read by the native SAM reader (include/svx_sam.h) whatever its record
-    order: the records are ordered in memory, `is_sam` is True, check_index() has nothing to ask for."""
+    order: the records are ordered in memory, `is_sam` is True, check_index() has nothing to ask for.
+    With `query` (the assembly FASTA the alignment was made from, plain or bgzip-compressed, with its .fai) the file is read
+    as minimap2's PAF with `cg:Z:` (include/svx_paf.h): `is_paf` is True (and `is_sam`: text input, ordered in memory), the
+    reference dictionary comes from `reference`.fai (the genome FASTA) and the bases from the query assembly."""
 
-    def __init__(self, path, mode="rb", threads=None, reader=None, device=None, verify=None):
+    def __init__(self, path, mode="rb", threads=None, reader=None, device=None, verify=None, query=None, reference=None):
         self.filename = path
         self._reader = reader or os.environ.get("SVX_BAM_READER", "native")
-        self.is_sam = is_sam(path)
+        self.is_paf = query is not None
+        self._query = None
+        if self.is_paf:
+            if reference is None:
+                raise ValueError("a PAF needs the reference FASTA's .fai for its dictionary")
+            from svim_asm_amd import fasta as _fasta
+            self._query = _fasta.FastaFile(query, device=device) if isinstance(query, str) else query
+            dictionary = read_fai_dictionary(reference)
+        self.is_sam = self.is_paf or is_sam(path)
         if self.is_sam:
             self._reader = "native"  # (the pure-Python walker reads BGZF only)
         self._loaded = None   # None: nothing; "all" or a tuple of tids
@@ -646,7 +698,7 @@ class AlignmentFile(object):
         self._pin_device = device
         if self._reader == "native":
             from svim_asm_amd import _lib
-            self._lib = lib = _SamApi(_lib.load()) if self.is_sam else _lib.load()
+            self._lib = lib = _PafApi(_lib.load(), dictionary) if self.is_paf else _SamApi(_lib.load()) if self.is_sam else _lib.load()
             h, err = C.c_void_p(), C.create_string_buffer(512)
             rc = lib.svx_bam_open(os.fsencode(path), int(threads or 0), C.byref(h), err, len(err))
             if rc != 0:
@@ -655,6 +707,8 @@ class AlignmentFile(object):
                     raise FileNotFoundError(msg)
                 raise ValueError(msg)
             self._h = h
+            if self.is_paf and lib.bind_query(h, self._query) != 0:
+                raise ValueError("%s: %s" % (path, lib.svx_bam_last_error(h).decode(errors="replace")))
             if verify is not None:  # None: the library's default (SVX_BAM_VERIFY); see include/svx_bam.h
                 lib.svx_bam_set_verify(h, 1 if verify else 0)
             text, l_text, n_ref = C.c_char_p(), C.c_uint64(), C.c_int32()
@@ -1037,6 +1091,9 @@ class AlignmentFile(object):
             self._c_cigar = None
             self._lib.svx_bam_close(self._h)
             self._h = None
+        if getattr(self, "_query", None) is not None:  # (behind the handle that reads from it)
+            self._query.close()
+            self._query = None
 
     def __del__(self):
         try:

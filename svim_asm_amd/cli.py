@@ -17,10 +17,12 @@ TYPE_LABELS = (("DEL", "deletion"), ("INV", "inversion"), ("INS", "insertion"), 
                ("DUP_INT", "interspersed duplication"), ("BND", "breakend"))
 
 
-def _open_file(path, options, one_shot=True, reader_threads=None):
+def _open_file(path, options, one_shot=True, reader_threads=None, query=None):
+    """`query`: the assembly FASTA of a PAF input (--query / --query1 / --query2); None: a BAM or a SAM, as ever."""
+    paf = {} if query is None else {"query": query, "reference": options.genome}
     f = bamio.AlignmentFile(path, device=getattr(options, "device", 0) or 0,
                             threads=reader_threads or bamio.quota_threads(2 if options.sub == "diploid" else 1, shard.world()[1]),
-                            verify=False if getattr(options, "no_bgzf_crc", False) else None)
+                            verify=False if getattr(options, "no_bgzf_crc", False) else None, **paf)
     # The device's share of the sequence slices' inflate work: the readers' own default (bamio.default_device_inflate_percent:
     # under a CPU quota the whole call — a fresh command's wall-clock is the same at every share, its CPU-seconds are 3.4 / 2.6 /
     # 2.0 at 0 / 50 / 100 %, profiles/r06_wave_cli_shares.txt; with a core per thread none).  The command's readers run on as
@@ -35,7 +37,7 @@ def _open_file(path, options, one_shot=True, reader_threads=None):
     return f
 
 
-def _open_ahead(path, options, one_shot=True, reader_threads=None):
+def _open_ahead(path, options, one_shot=True, reader_threads=None, query=None):
     """Start opening `path` (header, reference dictionary, index) on a thread; returns a function that waits and
     hands back the file — or raises what opening raised — at the point where the caller would have opened it."""
     import threading
@@ -43,7 +45,7 @@ def _open_ahead(path, options, one_shot=True, reader_threads=None):
 
     def run():
         try:
-            box["file"] = _open_file(path, options, one_shot, reader_threads)
+            box["file"] = _open_file(path, options, one_shot, reader_threads, query)
         except BaseException as e:  # noqa: BLE001 — re-raised by the caller at its own time
             box["error"] = e
     th = threading.Thread(target=run, daemon=True)
@@ -57,9 +59,39 @@ def _open_ahead(path, options, one_shot=True, reader_threads=None):
     return result
 
 
-def _open(path, which, options, opened=None):
+def _open_paf(path, which, options, opened, query):
+    """A PAF with its query assembly: the genome's messages for a FASTA that is missing, unindexed or unreadable."""
+    the = {"": "The", "first": "The first", "second": "The second"}[which]
+    if not os.path.exists(options.genome + ".fai"):
+        logging.error("The given reference genome is missing an index file ({0}.fai). A PAF input takes its contig names and "
+                      "lengths from it. Exiting..".format(options.genome))
+        return None
+    try:
+        aln_file = opened() if opened is not None else _open_file(path, options, query=query)
+    except MissingGziError:
+        logging.error("{0} query assembly is bgzip-compressed and is missing its index file ({1}.gzi). Exiting..".format(the, query))
+        return None
+    except BgzfFormatError as e:
+        logging.error("{0} query assembly cannot be read ({1}). Exiting..".format(the, e))
+        return None
+    except IOError:
+        logging.error("{0} query assembly is missing ({1}). Exiting..".format(the, query))
+        return None
+    except ValueError as e:
+        if not os.path.exists(query + ".fai"):
+            logging.error("{0} query assembly is missing an index file ({1}.fai). Exiting..".format(the, query))
+            return None
+        raise e
+    logging.info("{0} input is a PAF: its records are ordered in memory and their bases are read from the query assembly "
+                 "{1}.".format(the, query))
+    return aln_file
+
+
+def _open(path, which, options, opened=None, query=None):
     """Open one BAM and check sort order and index like the reference (svim-asm:63-72,85-95).
     Returns the alignment file, or None after logging the error."""
+    if query is not None:
+        return _open_paf(path, which, options, opened, query)
     the = {"": "Input", "first": "The first input", "second": "The second input"}[which]
     aln_file = opened() if opened is not None else _open_file(path, options)
     if getattr(aln_file, "is_sam", False):
@@ -197,7 +229,7 @@ def _run_steps(options):
     if options.sub == "haploid":
         logging.info("MODE: haploid")
         logging.info("INPUT: {0}".format(os.path.abspath(options.bam_file)))
-        aln_file1 = _open(options.bam_file, "", options)
+        aln_file1 = _open(options.bam_file, "", options, query=getattr(options, "query", None))
         if aln_file1 is None:
             return
         (sv_candidates,) = _collect([aln_file1], options)
@@ -205,11 +237,12 @@ def _run_steps(options):
         logging.info("MODE: diploid")
         logging.info("INPUT1: {0}".format(os.path.abspath(options.bam_file1)))
         logging.info("INPUT2: {0}".format(os.path.abspath(options.bam_file2)))
-        second = _open_ahead(options.bam_file2, options)  # opened beside the first one, judged in the reference's order
-        aln_file1 = _open(options.bam_file1, "first", options)
+        query1, query2 = getattr(options, "query1", None), getattr(options, "query2", None)
+        second = _open_ahead(options.bam_file2, options, query=query2)  # opened beside the first one, judged in the reference's order
+        aln_file1 = _open(options.bam_file1, "first", options, query=query1)
         if aln_file1 is None:
             return
-        aln_file2 = _open(options.bam_file2, "second", options, opened=second)
+        aln_file2 = _open(options.bam_file2, "second", options, opened=second, query=query2)
         if aln_file2 is None:
             return
         _timeline.mark("files open")

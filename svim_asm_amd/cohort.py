@@ -11,7 +11,8 @@ whatever the manifest's length.  The process pays interpreter start and HIP brin
     svim-asm-cohort haploid MANIFEST GENOME [--cohort_workers K] [--cohort_group G] [--cohort_threads T] [--cohort_lanes L] [the options of svim-asm haploid]
 
 MANIFEST: one sample per line, whitespace-separated — working_dir bam (haploid) or working_dir bam1 bam2 (diploid), each a
-sorted, indexed BAM or an uncompressed SAM in any record order;
+sorted, indexed BAM or an uncompressed SAM in any record order (PAF input is not taken here: a manifest line has no place
+for the query assembly a PAF needs, and the --query* options of `svim-asm haploid|diploid` are ignored by this command);
 lines starting with # are skipped.  Every sample gets its own working_dir/variants.vcf, byte-identical to the one
 the single-sample command writes.  K defaults to 4 (2 below 12 CPUs' worth of time), G to 1; `--cohort_group 0` = the whole
 manifest in one submission (the round-5 behaviour); T threads per BAM reader (default: the process's CPUs shared out among

@@ -49,6 +49,7 @@ constexpr uint64_t kArenaCap = 6ull << 30;  // device-resident inflated members 
 
 svx_inflate_launch_fn g_inflate = nullptr;   // svx_fasta_gather.hip registers the launches when the library loads
 svx_fasta_gather_fn g_gather = nullptr;
+svx_fasta_gather_oriented_fn g_gather_oriented = nullptr;
 svx_inflate_arena_fn g_arena = nullptr;
 
 bool host_only_env() {
@@ -275,8 +276,15 @@ struct Win {
     uint64_t b0, b1;
 };
 
-int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, bool upper,
-               const uint64_t* out_off, uint8_t* out, int n_threads, std::vector<Win>& wins) {
+// a window's bases as they lie in the file -> reversed and complemented when asked, every byte through the direction's table
+void orient(uint8_t* dst, size_t n, bool reversed, const uint8_t* tabs) {
+    if (reversed) std::reverse(dst, dst + n);
+    const uint8_t* t = tabs + (reversed ? 256 : 0);
+    for (size_t i = 0; i < n; ++i) dst[i] = t[dst[i]];
+}
+
+int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end,
+               const uint8_t* reverse, const uint8_t* tabs, bool upper, const uint64_t* out_off, uint8_t* out, int n_threads, std::vector<Win>& wins) {
     std::sort(wins.begin(), wins.end(), [](const Win& a, const Win& b) { return a.m0 != b.m0 ? a.m0 < b.m0 : a.i < b.i; });
     {
         std::lock_guard<std::mutex> lk(z->mu);
@@ -365,6 +373,7 @@ int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t
                     }
                     const int64_t e = std::min(end[W.i], g->length[ref[W.i]]);
                     lines_to_bases(g, ref[W.i], start[W.i], e, upper, raw.data(), nb, out + out_off[W.i]);
+                    if (tabs) orient(out + out_off[W.i], (size_t)(e - start[W.i]), reverse && reverse[W.i], tabs);
                 }
             }
         };
@@ -387,10 +396,10 @@ int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t
 
 // ------------------------------------------------------------------ device path
 // 1: done; 0: not taken (the caller runs the host path); < 0: a status to return
-int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, bool upper,
-                 const uint64_t* out_off, uint8_t* out, uint64_t out_lo, uint64_t out_bytes, int n_threads, const std::vector<Win>& wins) {
+int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end,
+                 const uint8_t* reverse, const uint8_t* tabs, bool upper, const uint64_t* out_off, uint8_t* out, uint64_t out_lo, uint64_t out_bytes, int n_threads, const std::vector<Win>& wins) {
     std::lock_guard<std::mutex> lk(z->mu);  // one device call of a handle at a time (arena, scratch, stream)
-    if (z->device < 0 || z->dev_broken || !g_inflate || !g_gather || !g_arena || host_only_env()) return 0;
+    if (z->device < 0 || z->dev_broken || !g_inflate || !g_gather || !g_arena || (tabs && !g_gather_oriented) || host_only_env()) return 0;
     std::vector<uint32_t> ms;
     for (const Win& w : wins)
         for (uint32_t m = w.m0; m <= w.m1; ++m) ms.push_back(m);
@@ -465,6 +474,10 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
             shift = 31 + c;
             magic = ((1ull << shift) / lb) + 1;
         }
+        // A reversed window is cut exactly like a forward one, in ascending SOURCE order, so that a chunk's bytes lie in
+        // two members at most whichever way its lanes walk them; only its place in the output differs: source bases
+        // [s, s + n) of a window that ends at e are output bases [e - s - n, e - s) of it (lane k: source s + n - 1 - k).
+        const bool rev = tabs && reverse && reverse[w.i];
         uint64_t s = (uint64_t)start[w.i], o = out_off[w.i];
         while (s < e) {
             const uint64_t u0 = off + (s / lb) * lw + s % lb;
@@ -477,7 +490,9 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
             const uint64_t before = (rel / lw) * lb + std::min<uint64_t>(rel % lw, lb);
             const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(e, before) - s, SVX_FASTA_CHUNK_BASES);
             svx_fasta_chunk c;
-            c.out = o;
+            c.out = rev ? out_off[w.i] + (e - s - n) : o;
+            c.reverse = rev ? 1u : 0u;
+            c.pad = 0;
             c.off = off;
             c.s0 = s;
             c.src_a = slot_of(ma);
@@ -503,10 +518,11 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     const uint64_t tab_bytes = (uint64_t)nf * 16 + (uint64_t)nf * 12;
     const uint64_t o_status = o_tab + up256(tab_bytes), o_ntok = o_status + up256((uint64_t)nf * 4);
     const uint64_t o_chunks = o_ntok + up256((uint64_t)nf * 4);
-    const uint64_t o_packed = o_chunks + up256(chunks.size() * sizeof(svx_fasta_chunk));
+    const uint64_t o_tabs = o_chunks + up256(chunks.size() * sizeof(svx_fasta_chunk));  // (the oriented gather's two tables)
+    const uint64_t o_packed = o_tabs + (tabs ? 512 : 0);
     const uint64_t o_tok = o_packed + up256(out_bytes + 8);
     const uint64_t need = o_tok + (nf ? up256((uint64_t)arena_members * SVX_INFLATE_TOK_STRIDE * 8) : 0);
-    const uint64_t stage_need = o_chunks + chunks.size() * sizeof(svx_fasta_chunk);  // everything that goes up
+    const uint64_t stage_need = tabs ? o_tabs + 512 : o_chunks + chunks.size() * sizeof(svx_fasta_chunk);  // everything that goes up
     if (z->scratch_cap < need) {
         if (z->d_scratch) {
             (void)hipStreamSynchronize(z->stream);
@@ -567,6 +583,10 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
         t_crc[k] = M.crc;
     }
     if (!chunks.empty()) memcpy(h + o_chunks, chunks.data(), chunks.size() * sizeof(svx_fasta_chunk));
+    if (tabs) {
+        memset(h + o_chunks + chunks.size() * sizeof(svx_fasta_chunk), 0, o_tabs - o_chunks - chunks.size() * sizeof(svx_fasta_chunk));
+        memcpy(h + o_tabs, tabs, 512);
+    }
     uint8_t* d = z->d_scratch;
     bool ok = hipMemcpyAsync(d, h, stage_need, hipMemcpyHostToDevice, z->stream) == hipSuccess;
     z->stat[2] += in_bytes;
@@ -575,8 +595,12 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
                        reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 20), reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 24), nf,
                        z->d_arena, reinterpret_cast<const uint64_t*>(d + o_tab + (uint64_t)nf * 8), reinterpret_cast<uint32_t*>(d + o_status),
                        reinterpret_cast<uint32_t*>(d + o_ntok), d + o_tok, arena_members) == 0;
-    ok = ok && g_gather(z->stream, z->d_arena, reinterpret_cast<const svx_fasta_chunk*>(d + o_chunks), (uint32_t)chunks.size(),
-                        upper ? 1 : 0, d + o_packed) == 0;
+    if (tabs)
+        ok = ok && g_gather_oriented(z->stream, z->d_arena, reinterpret_cast<const svx_fasta_chunk*>(d + o_chunks), (uint32_t)chunks.size(),
+                                     d + o_tabs, d + o_packed) == 0;
+    else
+        ok = ok && g_gather(z->stream, z->d_arena, reinterpret_cast<const svx_fasta_chunk*>(d + o_chunks), (uint32_t)chunks.size(),
+                            upper ? 1 : 0, d + o_packed) == 0;
     std::vector<uint32_t> status(nf);
     ok = ok && (nf == 0 || hipMemcpyAsync(status.data(), d + o_status, (size_t)nf * 4, hipMemcpyDeviceToHost, z->stream) == hipSuccess);
     ok = ok && (out_bytes == out_lo ||
@@ -597,8 +621,8 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     return 1;
 }
 
-int z_fetch(void* p, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, uint32_t n, int upper,
-            const uint64_t* out_off, uint8_t* out, int n_threads) {
+int z_fetch(void* p, const svx_fasta_geom* g, const int32_t* ref, const int64_t* start, const int64_t* end, const uint8_t* reverse,
+            const uint8_t* tabs, uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads) {
     Fz* z = static_cast<Fz*>(p);
     if (n_threads <= 0) n_threads = (int)std::min<unsigned>(16u, std::max<unsigned>(1u, std::thread::hardware_concurrency()));
     n_threads = std::min(n_threads, 16);
@@ -628,10 +652,10 @@ int z_fetch(void* p, const svx_fasta_geom* g, const int32_t* ref, const int64_t*
         wins.push_back(w);
     }
     if (wins.empty()) return SVX_OK;
-    const int d = device_fetch(z, g, ref, start, end, upper != 0, out_off, out, out_off[0], out_off[n], n_threads, wins);
+    const int d = device_fetch(z, g, ref, start, end, reverse, tabs, upper != 0, out_off, out, out_off[0], out_off[n], n_threads, wins);
     if (d < 0) return d;
     if (d == 1) return SVX_OK;
-    return host_fetch(z, g, ref, start, end, upper != 0, out_off, out, n_threads, wins);
+    return host_fetch(z, g, ref, start, end, reverse, tabs, upper != 0, out_off, out, n_threads, wins);
 }
 
 int z_set_device(void* p, int device, uint32_t min_members) {
@@ -666,8 +690,10 @@ const svx_fasta_bgzf_ops kOps = {z_open, z_close, z_fetch, z_set_device, z_stats
 
 }  // namespace
 
-extern "C" void svx_fasta_register_device(svx_inflate_launch_fn inflate, svx_fasta_gather_fn gather, svx_inflate_arena_fn arena) {
+extern "C" void svx_fasta_register_device(svx_inflate_launch_fn inflate, svx_fasta_gather_fn gather,
+                                          svx_fasta_gather_oriented_fn gather_oriented, svx_inflate_arena_fn arena) {
     g_inflate = inflate;
     g_gather = gather;
+    g_gather_oriented = gather_oriented;
     g_arena = arena;
 }

@@ -31,35 +31,14 @@
 
 #include "svx_cigartext_dev.h"
 #include "svx_sam.h"
+#include "svx_sam_internal.h"
 
 namespace {
 
+using namespace svx_samx;
+
 svx_cigar_text_launch_fn g_launch = nullptr;  // svx_cigartext.hip registers its launches when the library loads
 svx_cigar_text_ws_fn g_ws_need = nullptr;
-
-int thread_count(int asked) {
-    if (asked > 0) return std::min(asked, 64);
-    const unsigned hw = std::thread::hardware_concurrency();
-    return (int)std::max(1u, std::min(hw ? hw : 1u, 64u));
-}
-
-// fn(i) for i in [0, n) on up to `threads` threads; items are handed out one at a time (records differ 10^5-fold in size)
-template <typename F>
-void parallel_for(int threads, uint64_t n, F fn) {
-    if (n == 0) return;
-    const int t = (int)std::min<uint64_t>((uint64_t)std::max(1, threads), n);
-    if (t == 1) {
-        for (uint64_t i = 0; i < n; ++i) fn(i);
-        return;
-    }
-    std::atomic<uint64_t> next(0);
-    std::vector<std::thread> pool;
-    for (int k = 0; k < t; ++k)
-        pool.emplace_back([&] {
-            for (uint64_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i);
-        });
-    for (auto& th : pool) th.join();
-}
 
 inline bool is_digit(uint32_t c) { return c - '0' < 10u; }
 
@@ -130,33 +109,12 @@ struct SeqMap {
 };
 const SeqMap kSeqMap;
 
-struct Rec {
-    uint64_t line_off, file_idx;  // file_idx: (piece << 40 | place in the piece) until the pieces are joined
-    uint64_t name_off, cig_off, seq_off, seq_len, aux_off, aux_end;
-    uint32_t name_len, cig_len, line_local;  // line_local: place of the line in its piece, later its 1-based number
-    int32_t tid, pos;
-    uint16_t flag;
-    uint8_t mapq;
-};
-
 struct Piece {
     std::vector<Rec> recs;
     uint64_t n_lines = 0;      // line ends seen in the piece
     int64_t bad_line = -1;     // place (0-based, in the piece) of the first malformed line
     std::string bad_what;
 };
-
-bool parse_uint(const char* s, size_t n, uint64_t max, uint64_t* out) {
-    if (n == 0 || n > 19) return false;
-    uint64_t v = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (!is_digit((uint8_t)s[i])) return false;
-        v = v * 10 + (uint64_t)(s[i] - '0');
-    }
-    if (v > max) return false;
-    *out = v;
-    return true;
-}
 
 bool parse_int(const char* s, size_t n, int64_t lo, int64_t hi, int64_t* out) {
     bool neg = false;
@@ -288,44 +246,6 @@ hipStream_t device_stream(int device) {
 }
 
 }  // namespace
-
-struct svx_sam {
-    int fd = -1;
-    const char* map = nullptr;
-    size_t size = 0;
-    size_t body = 0;          // offset of the first line that is no header line
-    uint64_t header_lines = 0;
-    std::string text;
-    std::vector<std::string> ref_name;
-    std::vector<int32_t> ref_length;
-    std::unordered_map<std::string, int32_t> tid_of;
-    int n_threads = 1;
-    int pin_device = -1;
-    int device_parse = 1;
-    int parsed_on_device = 0;
-    std::string err;
-    // the loaded columns
-    uint64_t n = 0;
-    std::vector<Rec> recs;  // in the presented order
-    std::vector<int32_t> tid, pos, l_seq, ref_len;
-    std::vector<uint16_t> flag;
-    std::vector<uint8_t> mapq;
-    std::vector<uint64_t> cigar_off, name_off, aux_off, voffset;
-    std::vector<int64_t> sa_off;
-    std::vector<uint32_t> sa_len;
-    std::string names;
-    std::vector<uint8_t> aux;
-    uint32_t* cigar = nullptr;
-    bool cigar_pinned = false;
-    uint64_t n_ops = 0;
-    // device side
-    uint32_t* d_cigar = nullptr;
-    char* d_tmp = nullptr;
-    uint8_t* h_text = nullptr;  // page-locked copy of the gathered text
-    bool h_text_pinned = false;
-    hipEvent_t ready = nullptr;
-    bool d_valid = false;
-};
 
 namespace {
 
@@ -627,10 +547,7 @@ bool parse_on_device(svx_sam* s, uint64_t n_text, const std::vector<uint64_t>& r
 
 extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
     if (!s || (n_tids > 0 && !tids) || n_tids < 0) return SVX_E_INVALID;
-    if (s->pin_device >= 0 && hipSetDevice(s->pin_device) != hipSuccess) (void)hipGetLastError();
-    release_pool(s);
-    s->n = 0;
-    s->parsed_on_device = 0;
+    begin_load(s);
     const size_t n_ref = s->ref_name.size();
     std::vector<uint8_t> want;
     if (tids) {
@@ -676,12 +593,7 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
         }
     pieces.clear();
     std::sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) {
-        const uint32_t ta = (uint32_t)a.tid, tb = (uint32_t)b.tid;  // (-1 as the largest)
-        if (ta != tb) return ta < tb;
-        if (a.pos != b.pos) return a.pos < b.pos;
-        const int ra = (a.flag >> 4) & 1, rb = (b.flag >> 4) & 1;
-        if (ra != rb) return ra < rb;
-        return a.file_idx < b.file_idx;
+        return record_before(a.tid, a.pos, a.flag, a.file_idx, b.tid, b.pos, b.flag, b.file_idx);
     });
     const uint64_t n = s->n = recs.size();
     if (n >= 0xFFFFFFFFull) return fail(s, SVX_E_TOO_LARGE, "more than 2^32 - 2 records");
@@ -707,8 +619,27 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
         s->aux_off[i + 1] = s->aux.size();
         rec_off[i + 1] = rec_off[i] + r.cig_len;
     }
-    // 4. the CIGAR strings back to back (page-locked when the device is to read them) ...
-    const uint64_t n_text = rec_off[n];
+    // 4. the CIGAR strings back to back, then their words
+    if (!alloc_text(s, rec_off[n])) return fail(s, SVX_E_NOMEM, "no memory for the CIGAR text");
+    parallel_for(s->n_threads, n, [&](uint64_t i) { memcpy(s->h_text + rec_off[i], s->map + recs[i].cig_off, recs[i].cig_len); });
+    std::vector<uint32_t> line_of(n);
+    for (uint64_t i = 0; i < n; ++i) line_of[i] = recs[i].line_local;
+    return finish_cigars(s, rec_off, line_of, "the length of SEQ");
+}
+
+namespace svx_samx {
+
+const uint8_t* bam_alphabet() { return kSeqMap.m; }
+
+void begin_load(svx_sam* s) {
+    if (s->pin_device >= 0 && hipSetDevice(s->pin_device) != hipSuccess) (void)hipGetLastError();
+    release_pool(s);
+    s->n = 0;
+    s->parsed_on_device = 0;
+}
+
+// (page-locked when the device is to read the text)
+bool alloc_text(svx_sam* s, uint64_t n_text) {
     const bool want_device = s->pin_device >= 0 && s->device_parse && g_launch && n_text > 0;
     if (want_device && hipHostMalloc((void**)&s->h_text, n_text + 1, hipHostMallocDefault) == hipSuccess) {
         s->h_text_pinned = true;
@@ -716,10 +647,14 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
         (void)hipGetLastError();
         s->h_text = (uint8_t*)malloc(n_text + 1);
         s->h_text_pinned = false;
-        if (!s->h_text) return fail(s, SVX_E_NOMEM, "no memory for the CIGAR text");
     }
-    parallel_for(s->n_threads, n, [&](uint64_t i) { memcpy(s->h_text + rec_off[i], s->map + recs[i].cig_off, recs[i].cig_len); });
-    // ... and their words
+    return s->h_text != nullptr;
+}
+
+int finish_cigars(svx_sam* s, const std::vector<uint64_t>& rec_off, const std::vector<uint32_t>& line_of, const char* seq_what) {
+    const uint64_t n = s->n;
+    const uint64_t n_text = rec_off[n];
+    const bool want_device = s->h_text_pinned;
     std::vector<uint32_t> status(n, 0);
     if (want_device && parse_on_device(s, n_text, rec_off, &status)) {
         s->parsed_on_device = 1;
@@ -752,7 +687,7 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
     for (uint64_t r = 0; r < n; ++r)
         if (status[r] != SVX_CIGAR_OK) {
             const uint32_t st = status[r];
-            const uint32_t line = recs[r].line_local;
+            const uint32_t line = line_of[r];
             release_pool(s);
             s->n = 0;
             return fail(s, SVX_E_INVALID, "line " + std::to_string(line) + ": the CIGAR has " + cigar_status_text(st));
@@ -770,10 +705,10 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
         }
     });
     if (bad.load() >= 0) {
-        const uint32_t line = recs[(size_t)bad.load()].line_local;
+        const uint32_t line = line_of[(size_t)bad.load()];
         release_pool(s);
         s->n = 0;
-        return fail(s, SVX_E_INVALID, "line " + std::to_string(line) + ": the CIGAR's query length differs from the length of SEQ");
+        return fail(s, SVX_E_INVALID, "line " + std::to_string(line) + ": the CIGAR's query length differs from " + seq_what);
     }
     // the threads' pool goes up to where svx_collect_batch wants it
     if (!s->parsed_on_device && s->cigar_pinned && s->n_ops) {
@@ -794,6 +729,8 @@ extern "C" int svx_sam_load(svx_sam* s, const int32_t* tids, int32_t n_tids) {
     if (s->h_text && !s->h_text_pinned) { free(s->h_text); s->h_text = nullptr; }  // (a page-locked one waits for close: freeing it waits for the device)
     return SVX_OK;
 }
+
+}  // namespace svx_samx
 
 extern "C" int svx_sam_get_columns(const svx_sam* s, svx_bam_columns* c) {
     if (!s || !c) return SVX_E_INVALID;

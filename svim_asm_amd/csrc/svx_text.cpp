@@ -184,8 +184,43 @@ static bool fetch_one(const svx_fasta* fa, int32_t ref, int64_t start, int64_t e
     return true;
 }
 
-extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end,
-                                     uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads) {
+// One 256-entry table per direction: [0] a window as it lies in the file, [256] a reversed one (complement first, then
+// the alphabet).  Complement: A<->T C<->G M<->K R<->Y V<->B H<->D in either case; S W N = and everything else stay.
+struct OrientTables {
+    uint8_t t[2][512];  // [bam_alphabet]
+    OrientTables() {
+        uint8_t comp[256], bam[256];
+        for (int c = 0; c < 256; ++c) comp[c] = (uint8_t)c;
+        const char* pairs = "ATCGMKRYVBHD";
+        for (int k = 0; pairs[k]; k += 2) {
+            const uint8_t a = (uint8_t)pairs[k], b = (uint8_t)pairs[k + 1];
+            comp[a] = b; comp[b] = a;
+            comp[a + 32] = (uint8_t)(b + 32); comp[b + 32] = (uint8_t)(a + 32);
+        }
+        memset(bam, 'N', sizeof bam);
+        for (const char* p = "=ACMGRSVTWYHKDBN"; *p; ++p) {
+            bam[(uint8_t)*p] = (uint8_t)*p;
+            if (*p >= 'A' && *p <= 'Z') bam[(uint8_t)(*p + 32)] = (uint8_t)*p;
+        }
+        for (int c = 0; c < 256; ++c) {
+            t[0][c] = (uint8_t)c;
+            t[0][256 + c] = comp[c];
+            t[1][c] = bam[c];
+            t[1][256 + c] = bam[comp[c]];
+        }
+    }
+};
+static const OrientTables kOrient;
+
+// the window's bases as fetched (forward) -> what was asked for
+static void orient(uint8_t* dst, size_t n, bool reversed, const uint8_t* tabs) {
+    if (reversed) std::reverse(dst, dst + n);
+    const uint8_t* t = tabs + (reversed ? 256 : 0);
+    for (size_t i = 0; i < n; ++i) dst[i] = t[dst[i]];
+}
+
+static int fetch_impl(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end, const uint8_t* reverse,
+                      const uint8_t* tabs, uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads) {
     if (!fa || (n && (!ref || !start || !end || !out_off))) return SVX_E_INVALID;
     const int32_t n_refs = (int32_t)fa->length.size();
     // validate everything before a byte is written
@@ -198,7 +233,7 @@ extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, co
     if (n && out_off[n] && !out) return SVX_E_INVALID;
     if (fa->z) {
         const svx_fasta_geom g{n_refs, fa->length.data(), fa->offset.data(), fa->line_bases.data(), fa->line_width.data()};
-        return g_bgzf->fetch(fa->z, &g, ref, start, end, n, upper, out_off, out, n_threads);
+        return g_bgzf->fetch(fa->z, &g, ref, start, end, reverse, tabs, n, upper, out_off, out, n_threads);
     }
     if (n_threads <= 0) n_threads = (int)std::min<unsigned>(16u, std::max<unsigned>(1u, std::thread::hardware_concurrency()));
     if (n < 256) n_threads = 1;
@@ -212,7 +247,9 @@ extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, co
             const uint32_t hi = std::min<uint32_t>(n, lo + 512);
             for (uint32_t i = lo; i < hi; ++i) {
                 const int64_t e = std::min(end[i], fa->length[ref[i]]);
-                if (e > start[i] && !fetch_one(fa, ref[i], start[i], e, upper != 0, out + out_off[i], raw)) bad.store(1);
+                if (e <= start[i]) continue;
+                if (!fetch_one(fa, ref[i], start[i], e, upper != 0, out + out_off[i], raw)) bad.store(1);
+                else if (tabs) orient(out + out_off[i], (size_t)(e - start[i]), reverse && reverse[i], tabs);
             }
         }
     };
@@ -228,6 +265,17 @@ extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, co
         }
     }
     return bad.load() ? SVX_E_INVALID : SVX_OK;
+}
+
+extern "C" int svx_fasta_fetch_batch(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end,
+                                     uint32_t n, int upper, const uint64_t* out_off, uint8_t* out, int n_threads) {
+    return fetch_impl(fa, ref, start, end, nullptr, nullptr, n, upper, out_off, out, n_threads);
+}
+
+extern "C" int svx_fasta_fetch_oriented(const svx_fasta* fa, const int32_t* ref, const int64_t* start, const int64_t* end,
+                                        const uint8_t* reverse, uint32_t n, int bam_alphabet, const uint64_t* out_off, uint8_t* out,
+                                        int n_threads) {
+    return fetch_impl(fa, ref, start, end, reverse, kOrient.t[bam_alphabet ? 1 : 0], n, 0, out_off, out, n_threads);
 }
 
 // -------------------------------------------------------------------------------------------- VCF

@@ -168,6 +168,32 @@ class FastaFile(object):
             raise ValueError("reference windows shorter than the index says (%s)" % self.filename)
         return out, off.astype(np.int64)
 
+    def fetch_oriented(self, contigs, start, end, reverse, bam_alphabet=True):
+        """fetch_batch with a direction per window (svx_fasta_fetch_oriented, include/svx_text.h): window i is written as
+        its reverse complement where reverse[i] is set, and with `bam_alphabet` every byte goes through the 16 letters of a
+        BAM record's SEQ (lower case -> upper, anything else -> N).  (uint8 pool, int64 offsets [n + 1])."""
+        lib, h = self._handle()
+        n = len(contigs)
+        ref = np.fromiter((self._ref_index[c] for c in contigs), dtype=np.int32, count=n)
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        end = np.ascontiguousarray(end, dtype=np.int64)
+        reverse = np.ascontiguousarray(np.asarray(reverse).astype(bool), dtype=np.uint8)
+        if len(start) != n or len(end) != n or len(reverse) != n:
+            raise ValueError("fetch_oriented: columns of different lengths")
+        if n and (bool((start < 0).any()) or bool((end < start).any())):
+            raise ValueError("fetch coordinates out of range")
+        length = np.asarray(self.lengths, dtype=np.int64)[ref] if n else np.zeros(0, np.int64)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.maximum(np.minimum(end, length) - start, 0), out=off[1:])
+        out = np.empty(int(off[-1]), dtype=np.uint8)
+        rc = lib.svx_fasta_fetch_oriented(h, ref.ctypes.data, start.ctypes.data, end.ctypes.data, reverse.ctypes.data, n,
+                                          1 if bam_alphabet else 0, off.ctypes.data, out.ctypes.data, 0)
+        if rc != 0:
+            if self.compressed:
+                raise ValueError("%s: %s" % (self.filename, lib.svx_fasta_last_error(h).decode(errors="replace")))
+            raise ValueError("windows shorter than the index says (%s)" % self.filename)
+        return out, off.astype(np.int64)
+
     def stats(self):
         """Counters of a compressed file's fetches (all 0 for a plain one): members inflated on the host and on the
         device, compressed bytes staged for the device, cache hits, device calls, host calls."""
