@@ -530,9 +530,60 @@ def host_cpus():
     return hw
 
 
-def default_device_inflate_percent():
+def env_node_processes():
+    """SVX_NODE_PROCESSES as a positive integer — the cohort processes on this node, this one included (`svim-asm-cohort
+    --gpus N` sets it for its children; processes started by hand set it themselves) —, or None when it is unset, empty or
+    not a positive integer (said once on stderr, as env_device_inflate_percent does)."""
+    env = os.environ.get("SVX_NODE_PROCESSES")
+    if env in (None, ""):
+        return None
+    try:
+        n = int(env)
+        if n >= 1:
+            return n
+    except ValueError:
+        pass
+    if ("SVX_NODE_PROCESSES", env) not in _ENV_WARNED:
+        _ENV_WARNED.add(("SVX_NODE_PROCESSES", env))
+        import warnings
+        warnings.warn("SVX_NODE_PROCESSES=%r is not a positive integer: ignored, the process plans with the whole host" % env)
+    return None
+
+
+def process_cpus(siblings=None):
+    """CPUs' worth of time THIS process may plan with when `siblings` cohort processes (this one included: the argument,
+    else SVX_NODE_PROCESSES, else 1) share the node.  Alone: host_cpus(), exactly — the affinity mask is not looked at, so
+    nothing that ran before this existed sizes itself differently.  With siblings: the host's CPUs or the mask's, whichever
+    are fewer, shared out evenly, and never below 2 (the floor of every sizing rule that takes this).  A process computes it
+    ONCE, before it narrows its own mask (cohort.bind_to_device_node), and hands the figure down."""
+    if siblings is not None:
+        try:
+            ok = int(siblings) == siblings and int(siblings) >= 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            if ("siblings", repr(siblings)) not in _ENV_WARNED:
+                _ENV_WARNED.add(("siblings", repr(siblings)))
+                import warnings
+                warnings.warn("process_cpus(siblings=%r): not a positive integer, ignored" % (siblings,))
+            siblings = None
+    if siblings is None:
+        siblings = env_node_processes() or 1
+    siblings = int(siblings)
+    if siblings == 1:
+        return host_cpus()
+    cpus = host_cpus()
+    try:
+        cpus = min(cpus, float(len(os.sched_getaffinity(0))))
+    except (AttributeError, OSError):  # (a platform without the call: the host's figure)
+        pass
+    return max(2.0, cpus / siblings)
+
+
+def default_device_inflate_percent(cpus=None):
     """Share of a sequence-slice call the device inflates (svx_bam_set_device_inflate) unless SVX_BAM_DEVICE_INFLATE says
-    otherwise.  The device decodes a full-size sample's 14 k sequence members in ~17 ms (a wave per member,
+    otherwise; `cpus`: the budget the caller computed (process_cpus — per PROCESS, not per host, once cohort processes
+    share a node), None = process_cpus() now.  The device decodes a full-size sample's 14 k sequence members in ~17 ms (a wave per member,
     csrc/svx_inflate.hip) behind their staging; the host's threads take 45 ms for them when every thread has a core, but
     1.4 CPU-seconds of a run whose wall-clock IS its CPU-seconds over the CPUs it may use when those are few (the pool's
     16-CPU quota).  Measured there on the full-size sample (profiles/r06_wave_e2e.txt, r06_wave_cli_shares.txt): in one
@@ -542,7 +593,7 @@ def default_device_inflate_percent():
     asked = env_device_inflate_percent()
     if asked is not None:
         return asked
-    return 100 if host_cpus() <= 24 else 0
+    return 100 if (process_cpus() if cpus is None else cpus) <= 24 else 0
 
 
 def env_device_inflate_percent():

@@ -17,7 +17,18 @@ lines starting with # are skipped.  Every sample gets its own working_dir/varian
 the single-sample command writes.  K defaults to 4 (2 below 12 CPUs' worth of time), G to 1; `--cohort_group 0` = the whole
 manifest in one submission (the round-5 behaviour); T threads per BAM reader (default: the process's CPUs shared out among
 the readers in flight, default_reader_threads); L inflate lanes on the device (default_lanes: one per three readers in flight).  The reference has no such mode; this is an addition on top of the
-drop-in command, which is unchanged."""
+drop-in command, which is unchanged.
+
+    svim-asm-cohort haploid|diploid MANIFEST GENOME --gpus N [--devices d0,d1,...] [all other options]
+
+The command for a node: a parent that never touches the GPU deals the manifest out round-robin (sample i to child i mod N)
+and starts one fresh child per device — each of them the single-process command above on its own share with `--device d_k`.
+`--devices` names the device of each child (default 0..N-1, N of them, 1 <= N <= 16; an index may repeat: two processes then
+share that device); `--device` together with `--gpus` is an error.  Every child runs with SVX_NODE_PROCESSES=<children
+started>, from which it takes its share of the node's CPUs (bamio.process_cpus: workers, reader threads and the device's
+share of the inflate work follow the CPUs per PROCESS).  A failed child does not stop the others; the parent's status is the
+worst of theirs; SIGINT / SIGTERM are passed on as SIGTERM and answered with 130 / 143 once every child is gone.  Processes
+started by hand set SVX_NODE_PROCESSES themselves."""
 import gc
 import logging
 import os
@@ -43,17 +54,18 @@ def read_manifest(path, n_bams):
     return samples
 
 
-def _take_option(rest, name, default):
-    """Removes `name VALUE` (or name=VALUE) from the argument list of the reference's parser; returns int(VALUE)."""
+def _take_option(rest, name, default, convert=int):
+    """Removes `name VALUE` (or name=VALUE) from the argument list of the reference's parser; returns int(VALUE)
+    (convert(VALUE) where the value is not a number: --devices)."""
     out, value, k = [], default, 0
     while k < len(rest):
         a = rest[k]
         if a == name and k + 1 < len(rest):
-            value = int(rest[k + 1])
+            value = convert(rest[k + 1])
             k += 2
             continue
         if a.startswith(name + "="):
-            value = int(a.split("=", 1)[1])
+            value = convert(a.split("=", 1)[1])
             k += 1
             continue
         out.append(a)
@@ -103,14 +115,16 @@ def bind_to_device_node(device):
     return "device %d (%s): no NUMA node reported, threads not bound" % (device, addr or "address unknown")
 
 
-def default_workers():
+def default_workers(cpus=None):
+    """`cpus`: the process's budget (bamio.process_cpus, computed once by main before it binds its threads); None: asked now."""
     from svim_asm_amd import bamio
-    return 4 if bamio.host_cpus() >= 12 else 2
+    return 4 if (bamio.process_cpus() if cpus is None else cpus) >= 12 else 2
 
 
 def default_lanes(workers, n_bams):
-    """Inflate lanes for `workers` workers of `n_bams` readers each: one per three readers in flight, at least the library's
-    two.  A lane is held for a call's 50-70 ms and the workers are elsewhere most of the time, so a few lanes serve them;
+    """Inflate lanes for `workers` workers of `n_bams` readers each (the workers are what the process's CPU budget gave it:
+    default_workers): one per three readers in flight, at least the library's two.  A lane is held for a call's 50-70 ms and
+    the workers are elsewhere most of the time, so a few lanes serve them;
     every further lane that is busy at the same time shares the same host link and costs CPU-seconds (N = 16 full-size
     samples, 4 workers, one box, twice: 2 lanes 8.4-8.9 samples/s at 0.79 CPU-seconds per sample, 3 lanes 8.6-9.0 at 0.85,
     8 lanes 7.7-8.6 at 1.0; another box at N = 24 with a 400 ms wait: 6.2 on 2 lanes — calls that found no lane in time
@@ -119,15 +133,18 @@ def default_lanes(workers, n_bams):
     return max(2, min(16, (workers * n_bams + 1) // 3))
 
 
-def default_reader_threads(workers, n_bams):
-    """Threads per BAM reader: the CPUs' worth of time the process gets (hardware threads or the cgroup's quota) shared out
-    among the readers of the groups in flight.  Under a quota (cpu.max) a process that runs more threads than it has CPUs
+def default_reader_threads(workers, n_bams, cpus=None):
+    """Threads per BAM reader: the CPUs' worth of time the process gets (hardware threads or the cgroup's quota, divided by
+    the cohort processes on the node: bamio.process_cpus — `cpus` when the caller has computed it, which main does once, before
+    its workers narrow the affinity mask) shared out among the readers of the groups in flight.  Under a quota (cpu.max) a
+    process that runs more threads than it has CPUs
     spends a period's budget in a fraction of the period and then stands still for the rest of it: the single-sample command
     may do that once (its record walk is 1.3 CPU-seconds: inside one 100-ms budget of 16 CPUs), a process that works
     continuously must not."""
     from svim_asm_amd import bamio
     # (one and a half times the CPUs: a reader's threads also wait — for pages, for the device's share of the inflate work)
-    return max(2, int(round(1.5 * bamio.host_cpus() / float(max(1, workers * n_bams)))))
+    cpus = bamio.process_cpus() if cpus is None else cpus
+    return max(2, int(round(1.5 * cpus / float(max(1, workers * n_bams)))))
 
 
 def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader_threads=None):
@@ -190,6 +207,125 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
     return 0
 
 
+MAX_NODE_PROCESSES = 16  # (children with the GPU open at the same time; the parent is not one of them)
+
+
+def deal(samples, n):
+    """Sample i to child i mod n: the shares in child order, the empty ones of a short manifest included."""
+    return [samples[k::n] for k in range(n)]
+
+
+def _entry_script():
+    """The script the children run: the one this process was started as, else bin/svim-asm-cohort beside the package."""
+    if os.path.basename(sys.argv[0]) == "svim-asm-cohort" and os.path.isfile(sys.argv[0]):
+        return os.path.abspath(sys.argv[0])
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bin", "svim-asm-cohort")
+
+
+def _child_command(mode, share, genome, device, rest):
+    """argv of one child: today's single-process command on its share of the manifest (the seam a test replaces)."""
+    return [sys.executable, _entry_script(), mode, share, genome, "--device", str(device)] + list(rest)
+
+
+def _names_device(rest):
+    """Does the argument list give --device (in any spelling the reference's parser accepts)?"""
+    import argparse
+    sniff = argparse.ArgumentParser(add_help=False)
+    sniff.add_argument("--device", default=None)
+    try:
+        return sniff.parse_known_args(list(rest))[0].device is not None
+    except (SystemExit, Exception):  # noqa: BLE001 — `--device` without a value: named all the same
+        return True
+
+
+def _launch_plan(rest):
+    """(rest without --gpus / --devices, the device of each child) — or a message why the request is refused."""
+    try:
+        rest, gpus = _take_option(rest, "--gpus", None)
+        rest, devices = _take_option(rest, "--devices", None, convert=lambda v: [int(d) for d in v.split(",")])
+    except ValueError:
+        return None, "--gpus takes a number and --devices a comma-separated list of device indices"
+    if any(a in ("--gpus", "--devices") for a in rest):
+        return None, "--gpus and --devices each take a value"
+    if gpus is None:
+        return None, "--devices needs --gpus N"
+    if not 1 <= gpus <= MAX_NODE_PROCESSES:
+        return None, "--gpus %d: one child per device, 1 to %d of them" % (gpus, MAX_NODE_PROCESSES)
+    devices = list(range(gpus)) if devices is None else devices
+    if len(devices) != gpus or min(devices) < 0:
+        return None, "--devices names %d device(s) (none below 0) for --gpus %d" % (len(devices), gpus)
+    if _names_device(rest):
+        return None, "--device cannot be given together with --gpus: the parent gives each child its device (--devices)"
+    return rest, devices
+
+
+def launch(mode, manifest, genome, rest):
+    """`--gpus N`: the manifest dealt out to one fresh child process per device under one CPU budget (the module's
+    docstring).  This process creates no device context and does not load the library."""
+    import shutil
+    import signal
+    import subprocess
+    import tempfile
+    import threading
+    import time
+    rest, devices = _launch_plan(rest)
+    if rest is None:
+        print("svim-asm-cohort: " + devices, file=sys.stderr)
+        return 2
+    samples = read_manifest(manifest, 2 if mode == "diploid" else 1)  # (a malformed manifest fails here, before any child exists)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
+    shares = [(devices[k], share) for k, share in enumerate(deal(samples, len(devices))) if share]
+    env = dict(os.environ, SVX_NODE_PROCESSES=str(len(shares)))
+    tmp = tempfile.mkdtemp(prefix="svx-cohort-")
+    procs, caught = [], []
+
+    def stop_children(signo=None, frame=None):
+        if signo is not None:
+            caught.append(signo)
+        for p in procs:
+            if p.poll() is None:
+                p.send_signal(signal.SIGTERM)
+
+    handled = (signal.SIGINT, signal.SIGTERM) if threading.current_thread() is threading.main_thread() else ()
+    before = {s: signal.signal(s, stop_children) for s in handled}
+    try:
+        for k, (device, share) in enumerate(shares):
+            if caught:
+                break
+            path = os.path.join(tmp, "share_%d_of_%d.txt" % (k, len(shares)))
+            with open(path, "w") as f:
+                f.write("".join("%s %s\n" % (wd, " ".join(bams)) for wd, bams in share))
+            procs.append(subprocess.Popen(_child_command(mode, path, genome, device, rest), env=env))
+            if caught:  # (a signal that arrived while this child was being started has not reached it)
+                stop_children()
+        deadline = None
+        while any(p.poll() is None for p in procs):
+            if caught and deadline is None:
+                deadline = time.monotonic() + 10.0
+            if deadline is not None and time.monotonic() > deadline:
+                for p in procs:  # (a child that does not answer SIGTERM: nothing may outlive the parent)
+                    if p.poll() is None:
+                        p.kill()
+            time.sleep(0.02)
+    finally:
+        for p in procs:
+            if p.poll() is None:  # (an exception on the way: the same promise)
+                p.kill()
+            p.wait()
+        for s, handler in before.items():
+            signal.signal(s, handler)
+        shutil.rmtree(tmp, ignore_errors=True)
+    worst = 0
+    for p, (device, share) in zip(procs, shares):
+        rc = p.returncode
+        logging.info("CHILD: device %d, %d sample(s), %s", device, len(share),
+                     "status %d" % rc if rc >= 0 else "killed by signal %d" % -rc)
+        worst = max(worst, rc if rc >= 0 else 128 - rc)
+    if caught:
+        return 128 + int(caught[0])
+    return worst
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 3 or argv[0] not in ("haploid", "diploid"):
@@ -202,6 +338,8 @@ def main(argv=None):
         print("svim-asm-cohort runs as ONE process (WORLD_SIZE=%d): start one cohort per GPU with --device, or shard a "
               "single sample with `svim-asm` under the launcher" % shard.world()[1], file=sys.stderr)
         return 2
+    if any(a in ("--gpus", "--devices") or a.startswith(("--gpus=", "--devices=")) for a in rest):
+        return launch(mode, manifest, genome, rest)  # (the parent of one child per device: never touches the GPU itself)
     rest, workers = _take_option(rest, "--cohort_workers", 0)
     rest, per_group = _take_option(rest, "--cohort_group", 1)
     rest, reader_threads = _take_option(rest, "--cohort_threads", 0)
@@ -209,6 +347,10 @@ def main(argv=None):
     samples = read_manifest(manifest, n_bams)
     _timeline.mark("cohort main")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
+    # the CPUs this process plans with — ONCE, here: the workers narrow the affinity mask to the device's NUMA node
+    # (bind_to_device_node), and a budget read behind that would divide the narrowed mask among the siblings again
+    from svim_asm_amd import bamio
+    cpus = bamio.process_cpus()
     # one options object per sample through the reference's own parser (working dir and BAM paths differ)
     opts = [parse_arguments(cli.__version__, [mode, wd] + bams + [genome] + rest) for wd, bams in samples]
     device = getattr(opts[0], "device", 0) or 0
@@ -216,9 +358,13 @@ def main(argv=None):
     per_group = len(samples) if per_group <= 0 else per_group
     groups = [[(opts[k], samples[k][0], samples[k][1]) for k in range(g, min(g + per_group, len(samples)))]
               for g in range(0, len(samples), per_group)]
-    workers = max(1, min(workers or default_workers(), len(groups)))
+    workers = max(1, min(workers or default_workers(cpus), len(groups)))
+    reader_threads = reader_threads or default_reader_threads(workers, n_bams, cpus)
     logging.info("****************** %d samples, %d BAM files: %d group(s) of up to %d, %d worker(s) ******************",
                  len(samples), len(samples) * n_bams, len(groups), per_group, workers)
+    if bamio.env_node_processes() is not None:  # (one of a node's cohort processes: what it planned with, once)
+        logging.info("BUDGET: %.2f CPUs for this process (%d cohort process(es) on the node): %d worker(s), %d thread(s) per "
+                     "reader", cpus, bamio.env_node_processes(), workers, reader_threads)
     import threading
     from svim_asm_amd import _lib
     # inflate lanes of the device (svx_bam_set_inflate_lanes, before the first load): one per reader the workers keep in
@@ -248,7 +394,7 @@ def main(argv=None):
                     if g >= len(groups) or state["rc"] or state["error"]:
                         return
                     state["next"] = g + 1
-                rc = run_group(mode, groups[g], genome, get_ctx, g * per_group, len(samples), workers, reader_threads or None)
+                rc = run_group(mode, groups[g], genome, get_ctx, g * per_group, len(samples), workers, reader_threads)
                 if rc:
                     with lock:
                         state["rc"] = rc
