@@ -196,35 +196,11 @@ SYMBOLS = {
     "svx_bam_load": (C.c_int, [_P, _P, C.c_int32]),
     "svx_bam_get_columns": (C.c_int, [_P, _P]),
     "svx_bam_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
-    # native SAM ingest and the CIGAR-text parsers (include/svx_sam.h)
+    # native SAM and PAF ingest (include/svx_sam.h, include/svx_paf.h): what differs; the shared entry points follow the table
     "svx_sam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
-    "svx_sam_close": (None, [_P]),
-    "svx_sam_last_error": (C.c_char_p, [_P]),
-    "svx_sam_header": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
-    "svx_sam_reference": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
-    "svx_sam_set_pinned_device": (C.c_int, [_P, C.c_int]),
-    "svx_sam_set_device_parse": (C.c_int, [_P, C.c_int]),
-    "svx_sam_parsed_on_device": (C.c_int, [_P]),
-    "svx_sam_load": (C.c_int, [_P, _P, C.c_int32]),
-    "svx_sam_get_columns": (C.c_int, [_P, _P]),
-    "svx_sam_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
-    "svx_sam_device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
-    "svx_sam_device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
-    # native PAF ingest (include/svx_paf.h)
     "svx_paf_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
-    "svx_paf_close": (None, [_P]),
-    "svx_paf_last_error": (C.c_char_p, [_P]),
-    "svx_paf_header": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
-    "svx_paf_reference": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
-    "svx_paf_set_pinned_device": (C.c_int, [_P, C.c_int]),
-    "svx_paf_set_device_parse": (C.c_int, [_P, C.c_int]),
-    "svx_paf_parsed_on_device": (C.c_int, [_P]),
-    "svx_paf_load": (C.c_int, [_P, _P, C.c_int32]),
-    "svx_paf_get_columns": (C.c_int, [_P, _P]),
     "svx_paf_set_query": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
-    "svx_paf_seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
-    "svx_paf_device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
-    "svx_paf_device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    # the CIGAR-text parsers (include/svx_sam.h)
     "svx_cigar_text_parse": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_int]),
     "svx_cigar_text_parse_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
     "svx_inflate_raw": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -255,6 +231,23 @@ SYMBOLS = {
     "svx_tabix_build": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                   C.c_char_p, C.c_size_t]),
 }
+# the entry points the SAM and PAF readers share, declared once per prefix
+_TEXT_READER = {
+    "close": (None, [_P]),
+    "last_error": (C.c_char_p, [_P]),
+    "header": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "reference": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "set_pinned_device": (C.c_int, [_P, C.c_int]),
+    "set_device_parse": (C.c_int, [_P, C.c_int]),
+    "parsed_on_device": (C.c_int, [_P]),
+    "load": (C.c_int, [_P, _P, C.c_int32]),
+    "get_columns": (C.c_int, [_P, _P]),
+    "seq_slices": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
+    "device_pool": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P)]),
+    "device_pool_wait": (C.c_int, [_P, C.POINTER(C.c_double)]),
+}
+for _prefix in ("svx_sam_", "svx_paf_"):
+    SYMBOLS.update((_prefix + _name, _sig) for _name, _sig in _TEXT_READER.items())
 
 _lib = None
 

@@ -655,20 +655,17 @@ def is_sam(path):
         return False
 
 
-class _SamApi(object):
-    """The svx_sam_* entry points under the names AlignmentFile calls on a BAM handle; what only a BGZF file has (index,
-    CRC check, the device's share of the inflate work) is answered here."""
+class _TextApi(object):
+    """The entry points the SAM and PAF readers share (`prefix`: "svx_sam_" or "svx_paf_", include/svx_sam.h and
+    include/svx_paf.h) under the names AlignmentFile calls on a BAM handle.  What only a BGZF file has (index, CRC check,
+    the device's share of the inflate work) AlignmentFile answers itself for text input."""
 
-    def __init__(self, lib):
+    def __init__(self, lib, prefix):
         for name in ("open", "close", "last_error", "header", "reference", "set_pinned_device", "load", "get_columns",
                      "seq_slices", "device_pool", "device_pool_wait"):
-            setattr(self, "svx_bam_" + name, getattr(lib, "svx_sam_" + name))
-        self.svx_sam_set_device_parse = lib.svx_sam_set_device_parse
-        self.svx_sam_parsed_on_device = lib.svx_sam_parsed_on_device
-        for name in ("set_verify", "set_device_inflate", "set_device_inflate_min", "set_device_inflate_wait",
-                     "set_defer_verify", "verify_pending", "pending_members", "device_members"):
-            setattr(self, "svx_bam_" + name, lambda *a: 0)
-        self.svx_bam_index_state = lambda h: 0
+            setattr(self, "svx_bam_" + name, getattr(lib, prefix + name))
+        self.set_device_parse = getattr(lib, prefix + "set_device_parse")
+        self.parsed_on_device = getattr(lib, prefix + "parsed_on_device")
 
 
 def read_fai_dictionary(fasta_path):
@@ -683,23 +680,16 @@ def read_fai_dictionary(fasta_path):
     return names, lengths
 
 
-class _PafApi(_SamApi):
-    """The svx_paf_* entry points (include/svx_paf.h) under the names AlignmentFile calls on a BAM handle.  The reference
-    dictionary goes in at open; the bases come from the query assembly the handle is bound to (svx_paf_set_query)."""
+class _PafApi(_TextApi):
+    """The PAF reader: the reference dictionary goes in at open; the bases come from the query assembly the handle is
+    bound to (svx_paf_set_query)."""
 
     def __init__(self, lib, dictionary):
-        for name in ("close", "last_error", "header", "reference", "set_pinned_device", "load", "get_columns", "seq_slices",
-                     "device_pool", "device_pool_wait"):
-            setattr(self, "svx_bam_" + name, getattr(lib, "svx_paf_" + name))
-        self.svx_sam_set_device_parse = lib.svx_paf_set_device_parse
-        self.svx_sam_parsed_on_device = lib.svx_paf_parsed_on_device
-        for name in ("set_verify", "set_device_inflate", "set_device_inflate_min", "set_device_inflate_wait",
-                     "set_defer_verify", "verify_pending", "pending_members", "device_members"):
-            setattr(self, "svx_bam_" + name, lambda *a: 0)
-        self.svx_bam_index_state = lambda h: 0
+        _TextApi.__init__(self, lib, "svx_paf_")
         self._lib, self._dictionary = lib, dictionary
+        self.svx_bam_open = self._open
 
-    def svx_bam_open(self, path, threads, out, err, err_cap):
+    def _open(self, path, threads, out, err, err_cap):
         names, lengths = self._dictionary
         arr = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
         lens = np.asarray(lengths, dtype=np.int32)
@@ -749,7 +739,7 @@ class AlignmentFile(object):
         self._pin_device = device
         if self._reader == "native":
             from svim_asm_amd import _lib
-            self._lib = lib = _PafApi(_lib.load(), dictionary) if self.is_paf else _SamApi(_lib.load()) if self.is_sam else _lib.load()
+            self._lib = lib = _PafApi(_lib.load(), dictionary) if self.is_paf else _TextApi(_lib.load(), "svx_sam_") if self.is_sam else _lib.load()
             h, err = C.c_void_p(), C.create_string_buffer(512)
             rc = lib.svx_bam_open(os.fsencode(path), int(threads or 0), C.byref(h), err, len(err))
             if rc != 0:
@@ -760,7 +750,7 @@ class AlignmentFile(object):
             self._h = h
             if self.is_paf and lib.bind_query(h, self._query) != 0:
                 raise ValueError("%s: %s" % (path, lib.svx_bam_last_error(h).decode(errors="replace")))
-            if verify is not None:  # None: the library's default (SVX_BAM_VERIFY); see include/svx_bam.h
+            if verify is not None and not self.is_sam:  # None: the library's default (SVX_BAM_VERIFY); see include/svx_bam.h
                 lib.svx_bam_set_verify(h, 1 if verify else 0)
             text, l_text, n_ref = C.c_char_p(), C.c_uint64(), C.c_int32()
             tp = C.c_void_p()
@@ -798,6 +788,8 @@ class AlignmentFile(object):
     # ---------------------------------------------------------------- loading
     def index_state(self):
         """0 no index file, 1 usable .bai (parallel / per-contig walks), 2 present but unusable."""
+        if self.is_sam:
+            return 0
         if self._h is not None:
             return int(self._lib.svx_bam_index_state(self._h))
         base = self.filename
@@ -831,7 +823,7 @@ class AlignmentFile(object):
 
     @property
     def device_members(self):
-        return int(self._lib.svx_bam_device_members(self._h)) if self._h is not None else 0
+        return int(self._lib.svx_bam_device_members(self._h)) if self._h is not None and not self.is_sam else 0
 
     def set_device(self, device):
         """HIP device whose context page-locks the CIGAR pool of later loads (None: pageable)."""
@@ -867,12 +859,13 @@ class AlignmentFile(object):
             return self
         if self._h is not None:
             self._lib.svx_bam_set_pinned_device(self._h, -1 if self._pin_device is None else int(self._pin_device))
-            self._lib.svx_bam_set_device_inflate(self._h, 0 if self._pin_device is None else self.effective_device_inflate_percent())
-            self._lib.svx_bam_set_device_inflate_min(self._h, int(self.device_inflate_min_members))
-            self._lib.svx_bam_set_device_inflate_wait(self._h, int(self.device_inflate_wait_ms))
-            self._lib.svx_bam_set_defer_verify(self._h, 1 if self.defer_verify else 0)
             if self.is_sam:
-                self._lib.svx_sam_set_device_parse(self._h, 1 if sam_device_parse() else 0)
+                self._lib.set_device_parse(self._h, 1 if sam_device_parse() else 0)
+            else:
+                self._lib.svx_bam_set_device_inflate(self._h, 0 if self._pin_device is None else self.effective_device_inflate_percent())
+                self._lib.svx_bam_set_device_inflate_min(self._h, int(self.device_inflate_min_members))
+                self._lib.svx_bam_set_device_inflate_wait(self._h, int(self.device_inflate_wait_ms))
+                self._lib.svx_bam_set_defer_verify(self._h, 1 if self.defer_verify else 0)
             if tids is None:
                 rc = self._lib.svx_bam_load(self._h, None, 0)
             else:
@@ -889,12 +882,12 @@ class AlignmentFile(object):
     def verify_pending(self):
         """Check (on the reader's threads) the members the record walks took bytes from and no device leg has checked yet
         (defer_verify); ValueError for a damaged one, as load() itself raises without the deferral.  No-op otherwise."""
-        if self._h is not None and self._lib.svx_bam_verify_pending(self._h) != 0:
+        if self._h is not None and not self.is_sam and self._lib.svx_bam_verify_pending(self._h) != 0:
             raise ValueError("%s: %s" % (self.filename, self._lib.svx_bam_last_error(self._h).decode(errors="replace")))
 
     @property
     def pending_members(self):
-        return int(self._lib.svx_bam_pending_members(self._h)) if self._h is not None else 0
+        return int(self._lib.svx_bam_pending_members(self._h)) if self._h is not None and not self.is_sam else 0
 
     def _ensure(self):
         if self._loaded is None:
@@ -1096,7 +1089,7 @@ class AlignmentFile(object):
     @property
     def parsed_on_device(self):
         """SAM input: whether the loaded CIGAR words were written by the device's kernels (False: by the threads)."""
-        return bool(self.is_sam and self._h is not None and self._lib.svx_sam_parsed_on_device(self._h))
+        return bool(self.is_sam and self._h is not None and self._lib.parsed_on_device(self._h))
 
     def check_index(self):
         if self.is_sam:

@@ -1,5 +1,5 @@
-// svx_cigartext_dev.h — how svx_sam.cpp reaches the device parser of svx_cigartext.hip: through pointers that the
-// kernels' translation unit registers when the library loads (svx_sam.cpp also builds alone, for the CPU sanitizer tests).
+// svx_cigartext_dev.h — how svx_textaln.cpp reaches the device parser of svx_cigartext.hip: through pointers that the
+// kernels' translation unit registers when the library loads (svx_textaln.cpp also builds alone, for the CPU sanitizer tests).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,21 +1,17 @@
 // svx_paf.cpp — native PAF ingest (include/svx_paf.h): minimap2's `-c` output read into the columns of svx_bam.h, the
-// bases served from the query assembly.  A third front end of the shape of svx_sam.cpp:
-//   * the file is memory-mapped; the handle's threads cut it at line ends and take the twelve columns and the tp / cg / NM
-//     tags of every row
+// bases served from the query assembly.  A front end of svx_textaln.h, as svx_sam.cpp is:
+//   * the file is memory-mapped (MappedText); scan_lines cuts it at line ends on the handle's threads and parse_row takes
+//     the twelve columns and the tp / cg / NM tags of every row
 //   * flags (primary / supplementary by file order) and SA strings come from ALL rows of a query name, then the kept rows
 //     are ordered by svx_sam.h's comparison and every column is laid out in that order
-//   * per kept row the text `<clip5>S` + cg + `<clip3>S` is gathered back to back and handed to the SAM reader's
-//     finish_cigars (svx_sam_internal.h): device kernels or threads, pool in HBM, messages — nothing of it is restated here
+//   * per kept row the text `<clip5>S` + cg + `<clip3>S` is gathered back to back and handed to Columns::finish_cigars:
+//     device kernels or threads, pool in HBM, messages — nothing of it is restated here
 //   * svx_paf_seq_slices turns (record, begin, end) into oriented windows of the query FASTA (svx_fasta_fetch_oriented)
-// The columns live in a `svx_sam` without a file of its own, so get_columns / device_pool are the SAM reader's.
-#include <fcntl.h>
+// The handle holds its Columns by value: get_columns / device_pool and the error text are theirs.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <string>
@@ -24,16 +20,15 @@
 #include <vector>
 
 #include "svx_paf.h"
-#include "svx_sam_internal.h"
+#include "svx_textaln.h"
 
 namespace {
 
-using namespace svx_samx;
+using namespace svx_textaln;
 
-struct Row {
-    uint64_t line_off, file_idx;  // file_idx: (piece << 40 | place in the piece) until the pieces are joined
+struct Row : Line {
     uint64_t name_off, cg_off;
-    uint32_t name_len, cg_len, line;  // line: place of the line in its piece, later its 1-based number
+    uint32_t name_len, cg_len;
     int64_t nm;                       // -1: no NM:i tag
     int32_t qlen, qstart, qend, tid, tstart, tend;
     int32_t q_ref;                    // the query's place in the assembly's .fai (svx_paf_set_query)
@@ -41,27 +36,16 @@ struct Row {
     uint8_t mapq, rev, secondary, has_cg;
 };
 
-struct Piece {
-    std::vector<Row> rows;
-    uint64_t n_lines = 0;
-    int64_t bad_line = -1;
-    std::string bad_what;
-};
-
 }  // namespace
 
 struct svx_paf {
-    int fd = -1;
-    const char* map = nullptr;
-    size_t size = 0;
+    MappedText file;
     std::string text;  // the @SQ lines of the dictionary
     std::vector<std::string> ref_name;
     std::vector<int32_t> ref_length;
     std::unordered_map<std::string, int32_t> tid_of;
-    int n_threads = 1;
-    std::string err;
-    svx_sam* c = nullptr;    // the columns, the CIGAR pool and its copy in HBM
-    std::vector<Row> rows;   // the loaded rows in the presented order
+    Columns c;              // the columns, the CIGAR pool and its copy in HBM, the error text
+    std::vector<Row> rows;  // the loaded rows in the presented order
     // the assembly
     const svx_fasta* query = nullptr;
     std::unordered_map<std::string, std::pair<int32_t, int64_t>> query_of;  // name -> (place in the .fai, length)
@@ -70,10 +54,7 @@ struct svx_paf {
 
 namespace {
 
-int fail(svx_paf* p, int rc, const std::string& what) {
-    p->err = what;
-    return rc;
-}
+int fail(svx_paf* p, int rc, const std::string& what) { return p->c.fail(rc, what); }
 
 // clip5 / clip3 of the row's record (BAM orientation)
 inline uint32_t clip5(const Row& r) { return (uint32_t)(r.rev ? r.qlen - r.qend : r.qstart); }
@@ -94,7 +75,7 @@ std::string short_cigar(const Row& r) {
 
 // One row [a, e) (no line end, no '\r'): false with *what set when it is malformed.
 bool parse_row(const svx_paf* p, uint64_t a, uint64_t e, Row* r, std::string* what) {
-    const char* m = p->map;
+    const char* m = p->file.map;
     uint64_t f[13];  // starts of columns 0..11, f[12]: one behind the tab that ends column 11 (or e + 1)
     f[0] = a;
     uint64_t at = a;
@@ -111,7 +92,6 @@ bool parse_row(const svx_paf* p, uint64_t a, uint64_t e, Row* r, std::string* wh
     auto len = [&](int k) { return f[k + 1] - 1 - f[k]; };
     auto num = [&](int k, uint64_t max, uint64_t* v) { return parse_uint(m + f[k], len(k), max, v); };
     uint64_t qlen, qs, qe, tlen, ts, te, mq;
-    r->line_off = a;
     r->name_off = f[0];
     r->name_len = (uint32_t)std::min<uint64_t>(len(0), 0xFFFFFFFFu);
     if (!num(1, 0x7FFFFFFFu, &qlen)) { *what = "the query length (column 2) is not a number in 0..2^31-1"; return false; }
@@ -181,29 +161,6 @@ bool parse_row(const svx_paf* p, uint64_t a, uint64_t e, Row* r, std::string* wh
     return true;
 }
 
-void scan_piece(const svx_paf* p, uint64_t a, uint64_t b, uint64_t piece, Piece* out) {
-    const char* m = p->map;
-    while (a < b) {
-        const char* nl = (const char*)memchr(m + a, '\n', b - a);
-        uint64_t e = nl ? (uint64_t)(nl - m) : b;
-        const uint64_t next = e + 1;
-        if (e > a && m[e - 1] == '\r') --e;
-        if (e > a) {
-            Row r;
-            std::string what;
-            if (!parse_row(p, a, e, &r, &what)) {
-                if (out->bad_line < 0) { out->bad_line = (int64_t)out->n_lines; out->bad_what = what; }
-            } else {
-                r.line = (uint32_t)out->n_lines;
-                r.file_idx = (piece << 40) | out->rows.size();
-                out->rows.push_back(r);
-            }
-        }
-        ++out->n_lines;
-        a = next;
-    }
-}
-
 void put_nm(std::vector<uint8_t>* aux, int64_t nm) {
     aux->push_back('N');
     aux->push_back('M');
@@ -217,43 +174,30 @@ void put_nm(std::vector<uint8_t>* aux, int64_t nm) {
 
 extern "C" int svx_paf_open(const char* path, int32_t n_ref, const char* const* names, const int32_t* lengths, int n_threads,
                             svx_paf** out, char* err, size_t err_cap) {
+    svx_paf* p = nullptr;
     auto refuse = [&](int rc, const std::string& m) {
+        delete p;
         if (err && err_cap) snprintf(err, err_cap, "%s", m.c_str());
         if (out) *out = nullptr;
         return rc;
     };
     if (!path || !out || n_ref < 0 || (n_ref && (!names || !lengths))) return refuse(SVX_E_INVALID, "svx_paf_open: bad argument");
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return refuse(SVX_E_INVALID, std::string("cannot open ") + path);
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
-        close(fd);
-        return refuse(SVX_E_INVALID, std::string(path) + " is not a regular file");
+    p = new svx_paf();
+    p->c.n_threads = thread_count(n_threads);
+    auto bail = [&](const std::string& m) { return refuse(SVX_E_INVALID, m); };
+    switch (p->file.open(path)) {
+        case MappedText::CANNOT_OPEN: return bail(std::string("cannot open ") + path);
+        case MappedText::NOT_REGULAR: return bail(std::string(path) + " is not a regular file");
+        case MappedText::CANNOT_MAP: return refuse(SVX_E_NOMEM, std::string("cannot map ") + path);
+        case MappedText::GZIP: return bail(std::string(path) + " is gzip-compressed: a PAF is read as uncompressed text");
+        case MappedText::OK: break;
     }
-    svx_paf* p = new svx_paf();
-    p->fd = fd;
-    p->size = (size_t)st.st_size;
-    p->n_threads = thread_count(n_threads);
-    p->c = new svx_sam();
-    p->c->n_threads = p->n_threads;
-    auto bail = [&](const std::string& m) {
-        svx_paf_close(p);
-        return refuse(SVX_E_INVALID, m);
-    };
-    if (p->size) {
-        void* q = mmap(nullptr, p->size, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (q == MAP_FAILED) {
-            svx_paf_close(p);
-            return refuse(SVX_E_NOMEM, std::string("cannot map ") + path);
-        }
-        p->map = (const char*)q;
-    }
-    if (p->size >= 2 && (uint8_t)p->map[0] == 0x1f && (uint8_t)p->map[1] == 0x8b)
-        return bail(std::string(path) + " is gzip-compressed: a PAF is read as uncompressed text");
+    const char* map = p->file.map;
+    const size_t size = p->file.size;
     size_t at = 0;
-    while (at < p->size && (p->map[at] == '\n' || p->map[at] == '\r')) ++at;
-    if (at >= p->size) return bail(std::string(path) + " is empty: no PAF rows");
-    if (p->map[at] == '@')
+    while (at < size && (map[at] == '\n' || map[at] == '\r')) ++at;
+    if (at >= size) return bail(std::string(path) + " is empty: no PAF rows");
+    if (map[at] == '@')
         return bail(std::string(path) + " starts with a SAM header line: it is a SAM file, not a PAF (give it without a query FASTA)");
     for (int32_t k = 0; k < n_ref; ++k) {
         if (!names[k] || lengths[k] < 0) return bail("svx_paf_open: bad reference dictionary");
@@ -268,15 +212,9 @@ extern "C" int svx_paf_open(const char* path, int32_t n_ref, const char* const* 
     return SVX_OK;
 }
 
-extern "C" void svx_paf_close(svx_paf* p) {
-    if (!p) return;
-    svx_sam_close(p->c);  // (the pool, its copy in HBM, the event; it has no file of its own)
-    if (p->map) munmap((void*)p->map, p->size);
-    if (p->fd >= 0) close(p->fd);
-    delete p;
-}
+extern "C" void svx_paf_close(svx_paf* p) { delete p; }
 
-extern "C" const char* svx_paf_last_error(const svx_paf* p) { return p ? p->err.c_str() : "null handle"; }
+extern "C" const char* svx_paf_last_error(const svx_paf* p) { return p ? p->c.err.c_str() : "null handle"; }
 
 extern "C" int svx_paf_header(const svx_paf* p, const char** text, uint64_t* l_text, int32_t* n_ref) {
     if (!p) return SVX_E_INVALID;
@@ -293,14 +231,24 @@ extern "C" int svx_paf_reference(const svx_paf* p, int32_t tid, const char** nam
     return SVX_OK;
 }
 
-extern "C" int svx_paf_set_pinned_device(svx_paf* p, int device) { return p ? svx_sam_set_pinned_device(p->c, device) : SVX_E_INVALID; }
-extern "C" int svx_paf_set_device_parse(svx_paf* p, int on) { return p ? svx_sam_set_device_parse(p->c, on) : SVX_E_INVALID; }
-extern "C" int svx_paf_parsed_on_device(const svx_paf* p) { return p ? svx_sam_parsed_on_device(p->c) : 0; }
+extern "C" int svx_paf_set_pinned_device(svx_paf* p, int device) {
+    if (!p) return SVX_E_INVALID;
+    p->c.pin_device = device < 0 ? -1 : device;
+    return SVX_OK;
+}
+
+extern "C" int svx_paf_set_device_parse(svx_paf* p, int on) {
+    if (!p) return SVX_E_INVALID;
+    p->c.device_parse = on ? 1 : 0;
+    return SVX_OK;
+}
+
+extern "C" int svx_paf_parsed_on_device(const svx_paf* p) { return p ? p->c.parsed_on_device : 0; }
 
 extern "C" int svx_paf_load(svx_paf* p, const int32_t* tids, int32_t n_tids) {
     if (!p || (n_tids > 0 && !tids) || n_tids < 0) return SVX_E_INVALID;
-    svx_sam* c = p->c;
-    begin_load(c);
+    Columns* c = &p->c;
+    c->begin_load();
     p->rows.clear();
     p->query_bound = false;
     const size_t n_ref = p->ref_name.size();
@@ -312,37 +260,17 @@ extern "C" int svx_paf_load(svx_paf* p, const int32_t* tids, int32_t n_tids) {
             want[(size_t)tids[k]] = 1;
         }
     }
-    // 1. lines and columns: pieces of the mapping cut at line ends
-    const uint64_t n_pieces = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)p->n_threads * 4, p->size >> 16));
-    std::vector<uint64_t> cut(n_pieces + 1, p->size);
-    cut[0] = 0;
-    for (uint64_t k = 1; k < n_pieces; ++k) {
-        const uint64_t at = std::max(cut[k - 1], p->size / n_pieces * k);
-        const char* nl = at < p->size ? (const char*)memchr(p->map + at, '\n', p->size - at) : nullptr;
-        cut[k] = nl ? (uint64_t)(nl - p->map) + 1 : p->size;
-    }
-    std::vector<Piece> pieces(n_pieces);
-    parallel_for(p->n_threads, n_pieces, [&](uint64_t k) { scan_piece(p, cut[k], cut[k + 1], k, &pieces[k]); });
+    // 1. lines and columns
+    const char* map = p->file.map;
     std::vector<Row> all;
-    uint64_t lines_before = 0;
-    for (uint64_t k = 0; k < n_pieces; ++k) {
-        if (pieces[k].bad_line >= 0)
-            return fail(p, SVX_E_INVALID, "line " + std::to_string(lines_before + (uint64_t)pieces[k].bad_line + 1) + ": " + pieces[k].bad_what);
-        for (const Row& r0 : pieces[k].rows) {
-            Row r = r0;
-            r.file_idx = all.size();
-            r.line = (uint32_t)std::min<uint64_t>(lines_before + r0.line + 1, 0xFFFFFFFFu);  // from here on: the 1-based line
-            all.push_back(r);
-        }
-        lines_before += pieces[k].n_lines;
-    }
-    pieces.clear();
+    auto parse = [p](uint64_t a, uint64_t e, Row* r, std::string* what) { return parse_row(p, a, e, r, what); };
+    if (!scan_lines(p->file, 0, 0, c->n_threads, parse, &all, &c->err)) return SVX_E_INVALID;
     if (all.size() >= 0xFFFFFFFFull) return fail(p, SVX_E_TOO_LARGE, "more than 2^32 - 2 rows");
     // 2. the rows of every query name in file order: one length, primary / supplementary, the partners of the SA strings
     std::unordered_map<std::string_view, std::vector<uint32_t>> by_name;  // (the rows of a name that are not secondary)
     std::unordered_map<std::string_view, int32_t> qlen_of;
     for (Row& r : all) {
-        const std::string_view name(p->map + r.name_off, r.name_len);
+        const std::string_view name(map + r.name_off, r.name_len);
         auto q = qlen_of.emplace(name, r.qlen);
         if (!q.second && q.first->second != r.qlen)
             return fail(p, SVX_E_INVALID, "line " + std::to_string(r.line) + ": the query '" + std::string(name.substr(0, 80)) + "' has length " +
@@ -363,13 +291,9 @@ extern "C" int svx_paf_load(svx_paf* p, const int32_t* tids, int32_t n_tids) {
     std::sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
         return record_before(a.tid, a.tstart, a.flag, a.file_idx, b.tid, b.tstart, b.flag, b.file_idx);
     });
-    const uint64_t n = c->n = rows.size();
+    const uint64_t n = rows.size();
     // 4. fixed columns, names, aux (NM, SA)
-    c->tid.resize(n); c->pos.resize(n); c->l_seq.resize(n); c->ref_len.assign(n, 0); c->flag.resize(n); c->mapq.resize(n);
-    c->voffset.resize(n); c->sa_off.resize(n); c->sa_len.resize(n);
-    c->cigar_off.assign(n + 1, 0); c->name_off.assign(n + 1, 0); c->aux_off.assign(n + 1, 0);
-    c->names.clear();
-    c->aux.clear();
+    c->resize(n);
     std::vector<uint64_t> rec_off(n + 1, 0);
     std::vector<uint32_t> line_of(n);
     std::vector<std::string> head(n), tail(n);  // `<clip5>S` and `<clip3>S`
@@ -378,13 +302,13 @@ extern "C" int svx_paf_load(svx_paf* p, const int32_t* tids, int32_t n_tids) {
         c->tid[i] = r.tid; c->pos[i] = r.tstart; c->l_seq[i] = r.qlen; c->flag[i] = r.flag; c->mapq[i] = r.mapq;
         c->voffset[i] = r.line_off;
         line_of[i] = r.line;
-        c->names.append(p->map + r.name_off, r.name_len);
+        c->names.append(map + r.name_off, r.name_len);
         c->name_off[i + 1] = c->names.size();
         if (r.nm >= 0) put_nm(&c->aux, r.nm);
         c->sa_off[i] = -1;
         c->sa_len[i] = 0;
         if (!r.secondary) {
-            const std::vector<uint32_t>& group = by_name[std::string_view(p->map + r.name_off, r.name_len)];
+            const std::vector<uint32_t>& group = by_name[std::string_view(map + r.name_off, r.name_len)];
             if (group.size() > 1) {
                 std::string sa;
                 for (uint32_t k : group) {
@@ -409,42 +333,38 @@ extern "C" int svx_paf_load(svx_paf* p, const int32_t* tids, int32_t n_tids) {
             rec_off[i + 1] = rec_off[i] + 1;  // `*`: a tp:A:S row without cg
         }
     }
-    // 5. per record `<clip5>S` + cg + `<clip3>S` back to back, then the words: the SAM reader's two parsers
-    if (!alloc_text(c, rec_off[n])) return fail(p, SVX_E_NOMEM, "no memory for the CIGAR text");
-    parallel_for(p->n_threads, n, [&](uint64_t i) {
+    // 5. per record `<clip5>S` + cg + `<clip3>S` back to back, then the words
+    if (!c->alloc_text(rec_off[n])) return fail(p, SVX_E_NOMEM, "no memory for the CIGAR text");
+    parallel_for(p->c.n_threads, n, [&](uint64_t i) {
         const Row& r = rows[i];
         uint8_t* dst = c->h_text + rec_off[i];
         if (!r.has_cg) { *dst = '*'; return; }
         memcpy(dst, head[i].data(), head[i].size());
-        memcpy(dst + head[i].size(), p->map + r.cg_off, r.cg_len);
+        memcpy(dst + head[i].size(), map + r.cg_off, r.cg_len);
         memcpy(dst + head[i].size() + r.cg_len, tail[i].data(), tail[i].size());
     });
-    const int rc = finish_cigars(c, rec_off, line_of, "the row's query span (columns 4 - 3)");
+    const int rc = c->finish_cigars(rec_off, line_of, "the row's query span (columns 4 - 3)");
     if (rc != SVX_OK) {
         p->rows.clear();
-        return fail(p, rc, c->err);
+        return rc;
     }
     for (uint64_t i = 0; i < n; ++i)
         if (rows[i].has_cg && c->ref_len[i] != rows[i].tend - rows[i].tstart) {
             const uint32_t line = rows[i].line;
-            begin_load(c);
+            c->begin_load();
             p->rows.clear();
             return fail(p, SVX_E_INVALID, "line " + std::to_string(line) + ": the CIGAR's reference length differs from the row's target span (columns 9 - 8)");
         }
     return SVX_OK;
 }
 
-extern "C" int svx_paf_get_columns(const svx_paf* p, svx_bam_columns* out) { return p ? svx_sam_get_columns(p->c, out) : SVX_E_INVALID; }
+extern "C" int svx_paf_get_columns(const svx_paf* p, svx_bam_columns* out) { return p ? p->c.get_columns(out) : SVX_E_INVALID; }
 
 extern "C" int svx_paf_device_pool(svx_paf* p, const uint32_t** d_cigar, uint64_t* n_ops, void** ready) {
-    return p ? svx_sam_device_pool(p->c, d_cigar, n_ops, ready) : SVX_E_INVALID;
+    return p ? p->c.device_pool(d_cigar, n_ops, ready) : SVX_E_INVALID;
 }
 
-extern "C" int svx_paf_device_pool_wait(svx_paf* p, double* waited_us) {
-    if (!p) return SVX_E_INVALID;
-    const int rc = svx_sam_device_pool_wait(p->c, waited_us);
-    return rc == SVX_OK ? rc : fail(p, rc, p->c->err);
-}
+extern "C" int svx_paf_device_pool_wait(svx_paf* p, double* waited_us) { return p ? p->c.device_pool_wait(waited_us) : SVX_E_INVALID; }
 
 extern "C" int svx_paf_set_query(svx_paf* p, const svx_fasta* query, int32_t n_seq, const char* const* names, const int64_t* lengths) {
     if (!p || !query || n_seq < 0 || (n_seq && (!names || !lengths))) return SVX_E_INVALID;
@@ -466,7 +386,7 @@ extern "C" int svx_paf_seq_slices(svx_paf* p, const uint32_t* rec, const uint32_
     if (!p->query) return fail(p, SVX_E_INVALID, "svx_paf_seq_slices: no query assembly (svx_paf_set_query)");
     if (!p->query_bound) {
         for (Row& r : p->rows) {
-            const std::string name(p->map + r.name_off, r.name_len);
+            const std::string name(p->file.map + r.name_off, r.name_len);
             auto it = p->query_of.find(name);
             if (it == p->query_of.end())
                 return fail(p, SVX_E_INVALID, "line " + std::to_string(r.line) + ": the query '" + name.substr(0, 80) + "' is not in the query FASTA's index");
@@ -497,10 +417,10 @@ extern "C" int svx_paf_seq_slices(svx_paf* p, const uint32_t* rec, const uint32_
     }
     int rc;
     if (exact) {
-        rc = svx_fasta_fetch_oriented(p->query, ref.data(), start.data(), stop.data(), reverse.data(), n, 1, out_off, out, p->n_threads);
+        rc = svx_fasta_fetch_oriented(p->query, ref.data(), start.data(), stop.data(), reverse.data(), n, 1, out_off, out, p->c.n_threads);
     } else {  // slots wider than their slices: fetched back to back, then put in place
         std::vector<uint8_t> tmp(packed[n] + 1);
-        rc = svx_fasta_fetch_oriented(p->query, ref.data(), start.data(), stop.data(), reverse.data(), n, 1, packed.data(), tmp.data(), p->n_threads);
+        rc = svx_fasta_fetch_oriented(p->query, ref.data(), start.data(), stop.data(), reverse.data(), n, 1, packed.data(), tmp.data(), p->c.n_threads);
         for (uint32_t i = 0; rc == SVX_OK && i < n; ++i) memcpy(out + out_off[i], tmp.data() + packed[i], packed[i + 1] - packed[i]);
     }
     if (rc != SVX_OK) {

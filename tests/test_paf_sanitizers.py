@@ -25,7 +25,7 @@ def driver(request, tmp_path_factory):
     cmd = [gxx, "-std=c++17", "-g", "-O1", "-fsanitize=" + request.param, "-fno-sanitize-recover=all",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", csrc,
            os.path.join(ROOT, "tests", "native", "paf_sanitize.cpp"), os.path.join(csrc, "svx_paf.cpp"),
-           os.path.join(csrc, "svx_sam.cpp"), os.path.join(csrc, "svx_text.cpp"), "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
+           os.path.join(csrc, "svx_sam.cpp"), os.path.join(csrc, "svx_textaln.cpp"), os.path.join(csrc, "svx_text.cpp"), "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
            "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0:
