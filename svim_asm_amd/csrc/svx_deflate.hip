@@ -15,7 +15,7 @@
 //      slice of the block; the histograms are LDS counters.
 //   4. Dynamic Huffman codes (RFC 1951 §3.2.2): lengths by the two-queue method over the sorted frequencies, limited to
 //      15 bits (7 for the code-length alphabet) by moving leaves down/up until the Kraft sum is exactly 1; at least two
-//      codes per tree (zlib's rule), HLIT/HDIST/HCLEN with the run codes 16/17/18.
+//      codes per tree (zlib's rule), HLIT/HDIST/HCLEN with the run codes 16/17/18 (svx_deflate_huff.h).
 //   5. Bit lengths per token, a prefix sum per 256 tokens, ORs into LDS words.  A block whose DEFLATE form is not
 //      smaller than a stored block (BTYPE 00) is written stored instead: every member is at most 65 536 bytes.
 // A second kernel places the members one behind the other (their sizes scanned on the device) and appends the 28-byte
@@ -23,6 +23,7 @@
 // blocks are split across launches.
 #include <atomic>
 
+#include "svx_deflate_huff.h"
 #include "svx_internal.h"
 
 namespace {
@@ -52,14 +53,6 @@ struct DefArgs {
     uint32_t* tok;         // count * kBlk tokens
     uint32_t* mlen;        // member sizes, indexed by block
     uint32_t shift[6][32]; // x -> x * z^(8 * 1024 * 2^j) in CRC-32's field (svx_crc32_shift_columns)
-};
-
-// Huffman work areas, laid over the hash table once the parse is through
-struct HuffWork {
-    uint32_t key[288];
-    uint32_t w[576];
-    uint32_t par[576];
-    uint32_t blc[16];
 };
 
 struct Lds {
@@ -122,88 +115,6 @@ __device__ __forceinline__ void put_bits(Lds& s, uint32_t pos, uint32_t v, uint3
     const uint64_t x = (uint64_t)(v & (nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u))) << (pos & 31u);
     atomicOr(&s.data[pos >> 5], (uint32_t)x);
     if ((uint32_t)(x >> 32)) atomicOr(&s.data[(pos >> 5) + 1], (uint32_t)(x >> 32));
-}
-
-// Code lengths (<= maxbits) of a tree over n symbols with frequencies f, by one thread.  At least two codes: with fewer
-// used symbols, symbols 0 / 1 get length 1 (zlib's rule).  Lengths whose Kraft sum is exactly 1.
-__device__ void build_lengths(const uint32_t* f, int n, int maxbits, uint8_t* len, HuffWork& hw) {
-    int m = 0;
-    for (int i = 0; i < n; ++i) {
-        len[i] = 0;
-        if (f[i]) hw.key[m++] = (uint32_t)i;
-    }
-    if (m < 2) {
-        if (m == 0) { len[0] = 1; len[1] = 1; }
-        else { len[hw.key[0]] = 1; len[hw.key[0] == 0 ? 1 : 0] = 1; }
-        return;
-    }
-    // ascending (frequency, symbol): insertion sort (<= 286 symbols)
-    for (int i = 1; i < m; ++i) {
-        const uint32_t k = hw.key[i], fk = f[k];
-        int j = i - 1;
-        while (j >= 0 && (f[hw.key[j]] > fk || (f[hw.key[j]] == fk && hw.key[j] > k))) {
-            hw.key[j + 1] = hw.key[j];
-            --j;
-        }
-        hw.key[j + 1] = k;
-    }
-    // two queues: leaves 0..m-1 (sorted), internal nodes m.. in creation order (weights never decrease)
-    for (int i = 0; i < m; ++i) hw.w[i] = f[hw.key[i]];
-    int li = 0, ii = m, next = m;
-    for (int k = 0; k < m - 1; ++k) {
-        int a, b;
-        if (li < m && (ii >= next || hw.w[li] <= hw.w[ii])) a = li++; else a = ii++;
-        if (li < m && (ii >= next || hw.w[li] <= hw.w[ii])) b = li++; else b = ii++;
-        hw.w[next] = hw.w[a] + hw.w[b];
-        hw.par[a] = (uint32_t)next;
-        hw.par[b] = (uint32_t)next;
-        ++next;
-    }
-    // depths (reuse w): root = next - 1
-    hw.w[next - 1] = 0;
-    for (int i = next - 2; i >= 0; --i) hw.w[i] = hw.w[hw.par[i]] + 1u;
-    for (int b = 0; b <= 15; ++b) hw.blc[b] = 0;
-    for (int i = 0; i < m; ++i) hw.blc[hw.w[i] > (uint32_t)maxbits ? maxbits : hw.w[i]]++;
-    // Kraft sum in units of 2^-maxbits
-    uint32_t kraft = 0;
-    const uint32_t full = 1u << maxbits;
-    for (int b = 1; b <= maxbits; ++b) kraft += hw.blc[b] << (maxbits - b);
-    while (kraft > full) {  // lengthen a code of the deepest length below maxbits
-        int b = maxbits - 1;
-        while (hw.blc[b] == 0) --b;
-        hw.blc[b]--;
-        hw.blc[b + 1]++;
-        kraft -= 1u << (maxbits - b - 1);
-    }
-    while (kraft < full) {  // shorten a code of the deepest length: the smallest step
-        int b = maxbits;
-        while (hw.blc[b] == 0) --b;
-        hw.blc[b]--;
-        hw.blc[b - 1]++;
-        kraft += 1u << (maxbits - b);
-    }
-    // the longest codes to the rarest symbols
-    int at = 0;
-    for (int b = maxbits; b >= 1; --b)
-        for (uint32_t c = 0; c < hw.blc[b]; ++c) len[hw.key[at++]] = (uint8_t)b;
-}
-
-// canonical codes, bit-reversed for the LSB-first stream
-__device__ void make_codes(const uint8_t* len, int n, uint16_t* code) {
-    uint32_t cnt[16] = {0}, nxt[16];
-    for (int i = 0; i < n; ++i) cnt[len[i]]++;
-    cnt[0] = 0;
-    uint32_t c = 0;
-    for (int b = 1; b <= 15; ++b) {
-        c = (c + cnt[b - 1]) << 1;
-        nxt[b] = c;
-    }
-    for (int i = 0; i < n; ++i) {
-        const uint32_t l = len[i];
-        if (!l) { code[i] = 0; continue; }
-        const uint32_t v = nxt[l]++;
-        code[i] = (uint16_t)(__builtin_bitreverse32(v) >> (32 - l));
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_bgzf_deflate(DefArgs a) {
@@ -360,27 +271,7 @@ __global__ __launch_bounds__(kThreads) void k_bgzf_deflate(DefArgs a) {
         uint32_t hlit = 286, hdist = 30;
         while (hlit > 257 && s.lit_len[hlit - 1] == 0) --hlit;
         while (hdist > 1 && s.dist_len[hdist - 1] == 0) --hdist;
-        // run-length form of the lengths, HLIT then HDIST back to back (runs may cross: RFC 1951 §3.2.7)
-        const uint32_t total = hlit + hdist;
-        auto L = [&](uint32_t i) -> uint32_t { return i < hlit ? s.lit_len[i] : s.dist_len[i - hlit]; };
-        uint32_t nr = 0, i = 0;
-        while (i < total) {
-            const uint32_t v = L(i);
-            uint32_t run = 1;
-            while (i + run < total && L(i + run) == v) ++run;
-            if (v == 0) {
-                uint32_t left = run;
-                while (left >= 11) { const uint32_t r = left < 138 ? left : 138; s.rle[nr++] = (uint16_t)(18 | (r - 11) << 8); left -= r; }
-                if (left >= 3) { s.rle[nr++] = (uint16_t)(17 | (left - 3) << 8); left = 0; }
-                while (left) { s.rle[nr++] = 0; --left; }
-            } else {
-                s.rle[nr++] = (uint16_t)v;
-                uint32_t left = run - 1;
-                while (left >= 3) { const uint32_t r = left < 6 ? left : 6; s.rle[nr++] = (uint16_t)(16 | (r - 3) << 8); left -= r; }
-                while (left) { s.rle[nr++] = (uint16_t)v; --left; }
-            }
-            i += run;
-        }
+        const uint32_t nr = rle_lengths(s.lit_len, hlit, s.dist_len, hdist, s.rle);
         for (uint32_t k = 0; k < nr; ++k) s.cl_freq[s.rle[k] & 0xFFu]++;
         build_lengths(s.cl_freq, 19, 7, s.cl_len, s.u.h.cl);
         uint32_t hclen = 19;
