@@ -9,12 +9,10 @@
 //   * a `.bai` gives record boundaries (bin chunk begins/ends, linear index entries): the
 //     requested contigs' ranges are cut there into pieces of about equal compressed size and
 //     walked by a pool of threads, each with its own inflater;
-//   * inflate: the build's own DEFLATE decoder (svx_inflate.h; SVX_BAM_ZLIB=1: zlib, its oracle); the
-//     CRC32 of every member inflated to its end is checked, as htslib does (libdeflate's CRC routine
-//     when the runtime has the library — dlopen, optional —, zlib's otherwise).
+//   * members and their inflate come from svx_bgzf.h: the build's own DEFLATE decoder (SVX_BAM_ZLIB=1: zlib, its
+//     oracle); the CRC32 of every member inflated to its end is checked, as htslib does.
 #include "svx_bam.h"
 
-#include <dlfcn.h>
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -24,7 +22,6 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
@@ -38,174 +35,11 @@
 #include <vector>
 
 #include "svx.h"
-#include "svx_inflate.h"
-#include "svx_inflate_dev.h"
+#include "svx_bgzf.h"
 
 namespace {
 
-inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-inline uint32_t le32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
-
-// ------------------------------------------------------------------ optional libdeflate
-struct LibDeflate {
-    void* handle = nullptr;
-    void* (*alloc)(void) = nullptr;
-    int (*decompress)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
-    uint32_t (*crc32)(uint32_t, const void*, size_t) = nullptr;
-    void (*release)(void*) = nullptr;
-};
-
-const LibDeflate* libdeflate() {
-    static const LibDeflate lib = [] {
-        LibDeflate d;
-        const char* off = getenv("SVX_BAM_ZLIB");  // force the zlib path (tests)
-        if (off && off[0] == '1') return d;
-        void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return d;
-        d.alloc = reinterpret_cast<void* (*)(void)>(dlsym(h, "libdeflate_alloc_decompressor"));
-        d.decompress = reinterpret_cast<int (*)(void*, const void*, size_t, void*, size_t, size_t*)>(
-            dlsym(h, "libdeflate_deflate_decompress"));
-        d.crc32 = reinterpret_cast<uint32_t (*)(uint32_t, const void*, size_t)>(dlsym(h, "libdeflate_crc32"));
-        d.release = reinterpret_cast<void (*)(void*)>(dlsym(h, "libdeflate_free_decompressor"));
-        if (d.alloc && d.decompress && d.crc32 && d.release) d.handle = h;
-        else dlclose(h);
-        return d;
-    }();
-    return lib.handle ? &lib : nullptr;
-}
-
-// Which decoder inflates the members: the build's own (svx_inflate.h; default), or — SVX_BAM_ZLIB=1 — zlib, kept as
-// the differential oracle of the former.  libdeflate, when the runtime has it, only lends its CRC32 (carry-less
-// multiply: 64 KiB in a few µs where zlib's table walk takes 40).
-bool use_zlib() {
-    static const bool z = [] { const char* v = getenv("SVX_BAM_ZLIB"); return v && v[0] == '1'; }();
-    return z;
-}
-uint32_t member_crc(const uint8_t* p, size_t n) {
-    const LibDeflate* L = libdeflate();
-    if (L) return L->crc32(0, p, n);
-    return (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), p, (uInt)n);
-}
-
-struct Inflater {
-    z_stream zs;
-    bool z_ready = false;
-    std::unique_ptr<svx_inflate::Stream> own;
-    uint64_t n_blocks = 0;
-
-    Inflater() { memset(&zs, 0, sizeof(zs)); }
-    Inflater(const Inflater&) = delete;
-    Inflater& operator=(const Inflater&) = delete;
-    ~Inflater() {
-        if (z_ready) inflateEnd(&zs);
-    }
-    // Streaming use: begin() a member, then extend() the inflated prefix as far as somebody needs it.
-    // A slice of a contig-sized SEQ field sits somewhere inside a 64 KiB member: inflating only up to its last
-    // byte halves the work on average.  The CRC covers whole members, so it is checked when (and only when)
-    // the prefix reaches the member's end.
-    bool begin(const uint8_t* in, size_t in_len) {
-        ++n_blocks;
-        if (!use_zlib()) {
-            if (!own) own.reset(new svx_inflate::Stream());
-            own->begin(in, in_len);
-            return true;
-        }
-        if (!z_ready) {
-            if (inflateInit2(&zs, -15) != Z_OK) return false;
-            z_ready = true;
-        } else if (inflateReset(&zs) != Z_OK) {
-            return false;
-        }
-        zs.next_in = const_cast<Bytef*>(in);
-        zs.avail_in = (uInt)in_len;
-        return true;
-    }
-    // `out` holds `have` bytes of the member already (zlib: exactly; own decoder: at least — it may have run past the
-    // last request by up to one match, *valid is what is there now)
-    bool extend(uint8_t* out, size_t have, size_t want, size_t member_len, uint32_t crc, uint32_t* valid) {
-        const bool whole = want == member_len;
-        if (!use_zlib()) {
-            if (!own->run(out, member_len, want, whole)) return false;
-            *valid = (uint32_t)own->produced();
-            if (whole) return own->produced() == member_len && member_crc(out, member_len) == crc;
-            return true;
-        }
-        *valid = (uint32_t)want;
-        if (want <= have && !whole) return true;
-        zs.next_out = out + have;
-        zs.avail_out = (uInt)(want - have);
-        const int rc = inflate(&zs, whole ? Z_FINISH : Z_SYNC_FLUSH);
-        if (zs.avail_out != 0 || (rc != Z_OK && rc != Z_STREAM_END && rc != Z_BUF_ERROR)) return false;
-        if (whole) {
-            if (rc != Z_STREAM_END) return false;
-            return member_crc(out, member_len) == crc;
-        }
-        return true;
-    }
-    // One or two members at once, each inflated up to want[k] of its isize[k] bytes (want == isize: to the end, CRC32
-    // checked); with the build's own decoder two members are decoded side by side (svx_inflate::Stream::run_pair).
-    static bool run_two(Inflater inf[2], const uint8_t* const in[2], const size_t in_len[2], std::vector<uint8_t> buf[2],
-                        const size_t isize[2], const size_t want[2], const uint32_t crc[2], size_t n) {
-        if (n == 2 && !use_zlib()) {
-            for (int k = 0; k < 2; ++k) {
-                ++inf[k].n_blocks;
-                if (!inf[k].own) inf[k].own.reset(new svx_inflate::Stream());
-                inf[k].own->begin(in[k], in_len[k]);
-            }
-            bool ok[2] = {false, false};
-            svx_inflate::Stream::run_pair(*inf[0].own, buf[0].data(), isize[0], want[0], want[0] == isize[0], &ok[0],
-                                          *inf[1].own, buf[1].data(), isize[1], want[1], want[1] == isize[1], &ok[1]);
-            for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) return false;
-                if (want[k] == isize[k] && (inf[k].own->produced() != isize[k] || member_crc(buf[k].data(), isize[k]) != crc[k]))
-                    return false;
-            }
-            return true;
-        }
-        for (size_t k = 0; k < n; ++k) {
-            uint32_t valid = 0;
-            if (!inf[k].begin(in[k], in_len[k]) || !inf[k].extend(buf[k].data(), 0, want[k], isize[k], crc[k], &valid)) return false;
-        }
-        return true;
-    }
-    // raw deflate stream `in` → exactly out_len bytes, CRC32 checked
-    bool run(const uint8_t* in, size_t in_len, uint8_t* out, size_t out_len, uint32_t crc) {
-        uint32_t valid = 0;
-        return begin(in, in_len) && extend(out, 0, out_len, out_len, crc, &valid);
-    }
-};
-
-// ------------------------------------------------------------------ BGZF members
-struct Blk {
-    uint32_t bsize = 0, isize = 0, payload_off = 0, payload_len = 0, crc = 0;
-};
-
-// 0 ok, 1 clean end of file (coff == fsize), -1 malformed
-int parse_block(const uint8_t* map, uint64_t fsize, uint64_t coff, Blk* b) {
-    if (coff == fsize) return 1;
-    if (coff + 18 > fsize) return -1;
-    const uint8_t* p = map + coff;
-    if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || !(p[3] & 4)) return -1;
-    const uint32_t xlen = le16(p + 10);
-    if (coff + 12 + xlen + 8 > fsize) return -1;
-    uint32_t q = 12, end = 12 + xlen, bsize = 0;
-    while (q + 4 <= end) {
-        const uint32_t slen = le16(p + q + 2);
-        if (p[q] == 66 && p[q + 1] == 67 && slen == 2 && q + 6 <= end) bsize = (uint32_t)le16(p + q + 4) + 1;
-        q += 4 + slen;
-    }
-    if (!bsize || bsize < xlen + 20 || coff + bsize > fsize) return -1;
-    b->bsize = bsize;
-    b->payload_off = 12 + xlen;
-    b->payload_len = bsize - xlen - 20;
-    b->crc = le32(p + bsize - 8);
-    b->isize = le32(p + bsize - 4);
-    if (b->isize > 65536) return -1;
-    return 0;
-}
+using namespace svx_bgzf;  // Member, parse_member, Inflater, MemberTables, le16 / le32 / le64
 
 struct VPos {
     uint64_t coff = 0;
@@ -228,7 +62,7 @@ struct Cursor {
     Inflater* inf;
     uint64_t coff = 0;
     uint32_t uoff = 0;
-    Blk blk;
+    Member blk;
     bool eof = false;
     bool bad = false;
     uint64_t buf_coff = ~0ull;  // member currently held in `buf`
@@ -244,7 +78,7 @@ struct Cursor {
 
     bool settle() {  // make (coff, uoff) canonical; false on malformed data
         for (;;) {
-            const int rc = parse_block(f->map, f->fsize, coff, &blk);
+            const int rc = parse_member(f->map, f->fsize, coff, &blk);
             if (rc == 1) { eof = true; uoff = 0; return true; }
             if (rc < 0) { bad = true; return false; }
             if (uoff > blk.isize) { bad = true; return false; }
@@ -547,12 +381,12 @@ bool parse_bai(const std::vector<uint8_t>& d, int32_t n_ref_expected, std::vecto
 // specification): a BGZF file of its own — magic, min_shift, depth, auxiliary bytes, then per sequence the bins with
 // a `loffset` each (no linear index).  Gives the same thing a `.bai` does here: record boundaries.
 bool inflate_all(const std::vector<uint8_t>& raw, std::vector<uint8_t>* out) {
-    Inflater inf;
+    Inflater inf(use_zlib());
     uint64_t coff = 0;
     out->clear();
     for (;;) {
-        Blk blk;
-        const int rc = parse_block(raw.data(), raw.size(), coff, &blk);
+        Member blk;
+        const int rc = parse_member(raw.data(), raw.size(), coff, &blk);
         if (rc == 1) return true;
         if (rc < 0 || out->size() + blk.isize > (512u << 20)) return false;
         const size_t at = out->size();
@@ -1066,7 +900,7 @@ extern "C" int svx_bam_open(const char* path, int n_threads, svx_bam** out, char
         b->file.map = static_cast<const uint8_t*>(m);
     }
     // ---- header
-    Inflater inf;
+    Inflater inf(use_zlib());
     Cursor c(&b->file, &inf);
     uint8_t head[12];
     VPos zero;
@@ -1134,9 +968,9 @@ extern "C" int svx_bam_open(const char* path, int n_threads, svx_bam** out, char
                 std::atomic<bool> bad(false);
                 auto check = [&](size_t lo, size_t hi) {
                     for (size_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); ++i) {
-                        Blk blk;
+                        Member blk;
                         const uint64_t v = pts[i], co = v >> 16;
-                        const int rc = parse_block(b->file.map, b->file.fsize, co, &blk);
+                        const int rc = parse_member(b->file.map, b->file.fsize, co, &blk);
                         if (rc < 0 || (rc == 1 && (v & 0xFFFF)) || (rc == 0 && (v & 0xFFFF) > blk.isize)) bad.store(true);
                     }
                 };
@@ -1242,13 +1076,13 @@ static bool verify_members_on_host(svx_bam* b, const std::vector<uint64_t>& coff
     std::atomic<bool> bad(false);
     std::atomic<uint64_t> n_inflated(0);
     auto check = [&]() {
-        Inflater inf;
+        Inflater inf(use_zlib());
         std::vector<uint8_t> buf(65536);
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= coffs.size() || bad.load()) break;
-            Blk blk;
-            if (parse_block(b->file.map, b->file.fsize, coffs[i], &blk) != 0 ||
+            Member blk;
+            if (parse_member(b->file.map, b->file.fsize, coffs[i], &blk) != 0 ||
                 !inf.run(b->file.map + coffs[i] + blk.payload_off, blk.payload_len, buf.data(), blk.isize, blk.crc))
                 bad.store(true);
         }
@@ -1312,7 +1146,7 @@ struct Piece {
 
 // canonical position of a virtual offset (false: malformed)
 bool canonical(const File* f, uint64_t v, VPos* out) {
-    Inflater none;
+    Inflater none(use_zlib());
     Cursor c(f, &none);
     VPos p;
     p.coff = v >> 16;
@@ -1434,7 +1268,7 @@ extern "C" int svx_bam_load(svx_bam* b, const int32_t* tids, int32_t n_tids) {
     const bool deferred = b->verify && b->defer_verify && b->inflate_pct > 0 && b->pin_device >= 0 && b->pin_device < kMaxLanes &&
                           g_inflate_launch && g_gather_launch;
     auto worker = [&]() {
-        Inflater inf;
+        Inflater inf(use_zlib());
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= pieces.size() || failed.load()) break;
@@ -1672,7 +1506,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
     // (3) unpack the 4-bit codes of every piece from the two buffers.
     struct Job {   // one member and the prefix of it that is needed
         uint64_t coff;
-        Blk blk;
+        Member blk;
         uint32_t upto;
     };
     struct Piece {  // the part of slice `slice` that lies in member `job`: packed bytes [uoff, uoff + n) of the member
@@ -1680,7 +1514,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
         uint64_t first;  // index of its first packed byte within the record's SEQ field
     };
     struct State {
-        Inflater inf[2];
+        Inflater inf[2] = {Inflater(use_zlib()), Inflater(use_zlib())};
         std::vector<uint8_t> buf[2];
         std::vector<Job> jobs;
         std::vector<Piece> pieces;
@@ -1738,11 +1572,14 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
         for (size_t j = 0; j < st.jobs.size() && !failed.load(); j += 2) {
             const size_t nj = std::min<size_t>(2, st.jobs.size() - j);
             const uint8_t* in[2] = {nullptr, nullptr};
+            uint8_t* dst[2] = {nullptr, nullptr};
             size_t in_len[2] = {0, 0}, isize[2] = {0, 0}, want[2] = {0, 0};
             uint32_t crc[2] = {0, 0};
+            bool good[2];
             for (size_t k = 0; k < nj; ++k) {
                 const Job& jb = st.jobs[j + k];
                 if (st.buf[k].empty()) st.buf[k].resize(65536);
+                dst[k] = st.buf[k].data();
                 in[k] = b->file.map + jb.coff + jb.blk.payload_off;
                 in_len[k] = jb.blk.payload_len;
                 isize[k] = jb.blk.isize;
@@ -1753,7 +1590,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
                 if (known) n_known.fetch_add(1, std::memory_order_relaxed);
                 crc[k] = jb.blk.crc;
             }
-            if (!Inflater::run_two(st.inf, in, in_len, st.buf, isize, want, crc, nj)) { failed.store(true); return; }
+            if (!Inflater::run_two(st.inf, in, in_len, dst, isize, want, crc, nj, good)) { failed.store(true); return; }
             for (; pc < st.pieces.size() && st.pieces[pc].job < j + nj; ++pc) {
                 const Piece& p = st.pieces[pc];
                 unpack_piece(p, st.buf[p.job - j].data() + p.uoff);
@@ -1761,7 +1598,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
         }
     };
     auto work = [&](uint32_t lo, uint32_t hi) {
-        Inflater none;
+        Inflater none(use_zlib());
         Cursor c(&b->file, &none);
         State st;
         for (uint32_t at = lo; at < hi && !failed.load(); at += 32) work_on(c, st, at, std::min(hi, at + 32));
@@ -1836,7 +1673,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             // (1) locate
             std::atomic<uint32_t> next_run(0);
             auto locate_runs = [&]() {
-                Inflater none;
+                Inflater none(use_zlib());
                 Cursor c(&b->file, &none);
                 State st;
                 for (;;) {
@@ -1851,24 +1688,13 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             t_located = since_call_ms();
             ok = ok && !failed.load();
             // member and piece tables; device memory
-            std::vector<uint64_t> in_off, out_off_m;
-            std::vector<uint32_t> in_len, isz, crc;
-            std::vector<const uint8_t*> src;
-            uint64_t in_bytes = 0, out_bytes = 0, packed_bytes = 0;
+            MemberTables mt;  // (outputs from 0 of d_out)
+            uint64_t packed_bytes = 0;
             for (const RunPlan& pl : plans) {
-                const uint32_t base = (uint32_t)in_off.size();
-                for (const Job& jb : pl.jobs) {
-                    in_off.push_back(in_bytes);
-                    in_len.push_back(jb.blk.payload_len);
-                    isz.push_back(jb.blk.isize);
-                    crc.push_back(jb.blk.crc);
-                    out_off_m.push_back(out_bytes);
-                    src.push_back(b->file.map + jb.coff + jb.blk.payload_off);
-                    in_bytes += ((uint64_t)jb.blk.payload_len + 3) & ~3ull;
-                    out_bytes += ((uint64_t)jb.blk.isize + 8 + 15) & ~15ull;
-                }
+                const uint32_t base = mt.size();
+                for (const Job& jb : pl.jobs) mt.add(b->file.map, jb.coff, jb.blk);
                 for (const Piece& pc : pl.pieces) {
-                    g_src_off.push_back(out_off_m[base + pc.job] + pc.uoff);
+                    g_src_off.push_back(mt.out_off[base + pc.job] + pc.uoff);
                     g_len.push_back(pc.n);
                     g_dst_off.push_back(packed_bytes);
                     packed_bytes += pc.n;
@@ -1878,26 +1704,20 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             // members with no piece to gather — those that are not among the leg's own already
             if (!b->pending_members.empty()) {
                 std::vector<uint64_t> own;
-                own.reserve(in_off.size());
+                own.reserve(mt.size());
                 for (const RunPlan& pl : plans)
                     for (const Job& jb : pl.jobs) own.push_back(jb.coff);
                 std::sort(own.begin(), own.end());
                 for (const uint64_t coff : b->pending_members) {
                     if (std::binary_search(own.begin(), own.end(), coff)) continue;
-                    Blk blk;
-                    if (parse_block(b->file.map, b->file.fsize, coff, &blk) != 0) { failed.store(true); ok = false; break; }
-                    in_off.push_back(in_bytes);
-                    in_len.push_back(blk.payload_len);
-                    isz.push_back(blk.isize);
-                    crc.push_back(blk.crc);
-                    out_off_m.push_back(out_bytes);
-                    src.push_back(b->file.map + coff + blk.payload_off);
-                    in_bytes += ((uint64_t)blk.payload_len + 3) & ~3ull;
-                    out_bytes += ((uint64_t)blk.isize + 8 + 15) & ~15ull;
+                    Member blk;
+                    if (parse_member(b->file.map, b->file.fsize, coff, &blk) != 0) { failed.store(true); ok = false; break; }
+                    mt.add(b->file.map, coff, blk);
                     ++g_extra;
                 }
             }
-            g_members = (uint32_t)in_off.size();
+            g_members = mt.size();
+            const uint64_t in_bytes = mt.in_bytes, out_bytes = mt.out_end;
             // A set of launches costs one member's latency on the device (3-4 ms) and the leg its staging: below a few
             // hundred members the threads are through sooner (svx_bam_set_device_inflate_min, default 500; config 5's
             // 1 200-member calls: the same wall-clock on the device for 0.6 of 1.0 CPU-seconds).
@@ -1905,7 +1725,8 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             const uint32_t n_pc = (uint32_t)g_len.size();
             auto up256 = [](uint64_t x) { return (x + 255) & ~255ull; };
             const uint64_t o_in = 0, o_out = up256(in_bytes + 8), o_tab = o_out + up256(out_bytes + 16);
-            const uint64_t tab_bytes = (uint64_t)g_members * 28 + (uint64_t)n_pc * 20 + 256;
+            const uint64_t o_pieces = (mt.bytes() + 7) & ~7ull;  // the piece tables behind the members', within the blob
+            const uint64_t tab_bytes = o_pieces + (uint64_t)n_pc * 20 + 256;
             // the two-pass kernels' token lists: an arena for SVX_INFLATE_ARENA_MEMBERS members at a time (svx_inflate_dev.h)
             const uint32_t arena_members = std::min<uint32_t>(g_members, SVX_INFLATE_ARENA_MEMBERS);
             const uint64_t o_status = o_tab + up256(tab_bytes), o_packed = o_status + up256((uint64_t)g_members * 4);
@@ -1925,27 +1746,23 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             } else {
                 ok = false;
             }
-            // the tables as one blob: in_off | out_off | src_off | dst_off (u64) | in_len | isize | crc | len (u32)
+            // the tables as one blob: the members' (MemberTables::write) | src_off | dst_off (u64) | len (u32) of the pieces
             std::vector<uint8_t> blob;
-            uint64_t t_in_off = 0, t_out_off = 0, t_src_off = 0, t_dst_off = 0, t_in_len = 0, t_isz = 0, t_crc = 0, t_len = 0;
+            const uint64_t t_src_off = o_pieces, t_dst_off = t_src_off + (uint64_t)n_pc * 8, t_len = t_dst_off + (uint64_t)n_pc * 8;
             if (ok) {
-                auto put = [&](const void* ptr, size_t bytes) { const uint64_t at = blob.size(); blob.insert(blob.end(), (const uint8_t*)ptr, (const uint8_t*)ptr + bytes); return at; };
-                t_in_off = put(in_off.data(), (size_t)g_members * 8);
-                t_out_off = put(out_off_m.data(), (size_t)g_members * 8);
-                t_src_off = put(g_src_off.data(), (size_t)n_pc * 8);
-                t_dst_off = put(g_dst_off.data(), (size_t)n_pc * 8);
-                t_in_len = put(in_len.data(), (size_t)g_members * 4);
-                t_isz = put(isz.data(), (size_t)g_members * 4);
-                t_crc = put(crc.data(), (size_t)g_members * 4);
-                t_len = put(g_len.data(), (size_t)n_pc * 4);
+                blob.resize(t_len + (size_t)n_pc * 4);
+                mt.write(blob.data());
+                memcpy(blob.data() + t_src_off, g_src_off.data(), (size_t)n_pc * 8);
+                memcpy(blob.data() + t_dst_off, g_dst_off.data(), (size_t)n_pc * 8);
+                memcpy(blob.data() + t_len, g_len.data(), (size_t)n_pc * 4);
                 ok = blob.size() <= tab_bytes &&
                      hipMemcpyAsync(b->d_inflate + o_tab, blob.data(), blob.size(), hipMemcpyHostToDevice, lane->stream) == hipSuccess;
             }
             // (2) payloads through the ring: batch i = members [cut[i], cut[i + 1]) in slot i % kRingSlots
             std::vector<uint32_t> cut(1, 0);
             for (uint32_t m = 0; ok && m < g_members; ++m) {
-                const uint64_t end_m = (m + 1 < g_members ? in_off[m + 1] : in_bytes);
-                if (end_m - in_off[cut.back()] > kSlotBytes) cut.push_back(m);
+                const uint64_t end_m = (m + 1 < g_members ? mt.in_off[m + 1] : in_bytes);
+                if (end_m - mt.in_off[cut.back()] > kSlotBytes) cut.push_back(m);
             }
             cut.push_back(g_members);
             std::atomic<uint32_t> next_batch(0), phase_end(0), slot_gen[kRingSlots];
@@ -1967,9 +1784,9 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
                     bool good = gen == 0 || hipEventSynchronize(lane->slot_done[q]) == hipSuccess;  // ... and the copy has read the slot
                     const int64_t t2 = debug ? now_us() : 0;
                     uint8_t* slot = lane->ring + (size_t)q * kSlotBytes;
-                    const uint64_t b0 = in_off[cut[i]];
-                    const uint64_t b1 = cut[i + 1] < g_members ? in_off[cut[i + 1]] : in_bytes;
-                    for (uint32_t m = cut[i]; good && m < cut[i + 1]; ++m) memcpy(slot + (in_off[m] - b0), src[m], in_len[m]);
+                    const uint64_t b0 = mt.in_off[cut[i]];
+                    const uint64_t b1 = cut[i + 1] < g_members ? mt.in_off[cut[i + 1]] : in_bytes;
+                    for (uint32_t m = cut[i]; good && m < cut[i + 1]; ++m) memcpy(slot + (mt.in_off[m] - b0), mt.src[m], mt.in_len[m]);
                     const int64_t t3 = debug ? now_us() : 0;
                     good = good && hipMemcpyAsync(b->d_inflate + o_in + b0, slot, b1 - b0, hipMemcpyHostToDevice, lane->stream) == hipSuccess &&
                            hipEventRecord(lane->slot_done[q], lane->stream) == hipSuccess;
@@ -2000,10 +1817,8 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
                 if (n_phases > 1)
                     ok = ok && hipEventRecord(lane->staged[ph], lane->stream) == hipSuccess && hipStreamWaitEvent(ks, lane->staged[ph], 0) == hipSuccess;
                 ok = ok &&
-                     g_inflate_launch(ks, d + o_in, (const uint64_t*)(tab + t_in_off) + m0, (const uint32_t*)(tab + t_in_len) + m0,
-                                      (const uint32_t*)(tab + t_isz) + m0, (const uint32_t*)(tab + t_crc) + m0, m1 - m0, d + o_out,
-                                      (const uint64_t*)(tab + t_out_off) + m0, (uint32_t*)(d + o_status) + m0, (uint32_t*)(d + o_ntok) + m0,
-                                      d + o_tok, arena_members) == 0;
+                     mt.launch(g_inflate_launch, ks, d + o_in, tab, m0, m1, d + o_out, (uint32_t*)(d + o_status), (uint32_t*)(d + o_ntok),
+                               d + o_tok, arena_members) == 0;
                 if (ph == 0) t_staged = since_call_ms();  // (the first phase's: what the kernels wait for at least)
             }
             if (debug)
@@ -2036,7 +1851,7 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
             timespec c0;
             clock_gettime(CLOCK_THREAD_CPUTIME_ID, &c0);
             const auto w0 = std::chrono::steady_clock::now();
-            Inflater none;
+            Inflater none(use_zlib());
             Cursor c(&b->file, &none);  // only walks member headers here
             State st;
             for (;;) {
@@ -2128,41 +1943,5 @@ extern "C" int svx_bam_seq_slices(svx_bam* b, const uint32_t* rec, const uint32_
                 "%zu members verified by walks\n", (unsigned long long)n_jobs.load(), (unsigned long long)n_known.load(),
                 b->verified_members.size());
     if (failed.load()) return fail(b, SVX_E_INVALID, "svx_bam_seq_slices: bad slice bounds or malformed BGZF data");
-    return SVX_OK;
-}
-
-extern "C" int svx_inflate_raw(const uint8_t* in, size_t in_len, uint8_t* out, size_t cap, const uint64_t* stops,
-                               uint32_t n_stops, uint64_t* n_out) {
-    if ((!in && in_len) || (!out && cap) || (!stops && n_stops) || !n_out) return SVX_E_INVALID;
-    *n_out = 0;
-    std::unique_ptr<svx_inflate::Stream> st(new svx_inflate::Stream());
-    st->begin(in, in_len);
-    for (uint32_t i = 0; i < n_stops; ++i) {
-        const bool ok = st->run(out, cap, (size_t)std::min<uint64_t>(stops[i], cap), false);
-        *n_out = st->produced();
-        if (!ok) return SVX_E_INVALID;
-    }
-    const bool ok = st->run(out, cap, 0, true);
-    *n_out = st->produced();
-    return ok ? SVX_OK : SVX_E_INVALID;
-}
-
-extern "C" int svx_inflate_raw_pair(const uint8_t* in_a, size_t in_len_a, uint8_t* out_a, size_t cap_a, uint64_t stop_a,
-                                    uint64_t* n_out_a, int* rc_a, const uint8_t* in_b, size_t in_len_b, uint8_t* out_b,
-                                    size_t cap_b, uint64_t stop_b, uint64_t* n_out_b, int* rc_b) {
-    if ((!in_a && in_len_a) || (!out_a && cap_a) || (!in_b && in_len_b) || (!out_b && cap_b) || !n_out_a || !n_out_b ||
-        !rc_a || !rc_b)
-        return SVX_E_INVALID;
-    std::unique_ptr<svx_inflate::Stream> a(new svx_inflate::Stream()), b(new svx_inflate::Stream());
-    a->begin(in_a, in_len_a);
-    b->begin(in_b, in_len_b);
-    bool ok_a = false, ok_b = false;
-    const bool end_a = stop_a == ~0ull, end_b = stop_b == ~0ull;
-    svx_inflate::Stream::run_pair(*a, out_a, cap_a, end_a ? 0 : (size_t)std::min<uint64_t>(stop_a, cap_a), end_a, &ok_a,
-                                  *b, out_b, cap_b, end_b ? 0 : (size_t)std::min<uint64_t>(stop_b, cap_b), end_b, &ok_b);
-    *n_out_a = a->produced();
-    *n_out_b = b->produced();
-    *rc_a = ok_a ? SVX_OK : SVX_E_INVALID;
-    *rc_b = ok_b ? SVX_OK : SVX_E_INVALID;
     return SVX_OK;
 }

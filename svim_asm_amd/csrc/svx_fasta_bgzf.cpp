@@ -5,7 +5,7 @@
 // uncompressed bytes; a window [start, end) of a sequence is the byte range fetch_one of svx_text.cpp reads, and the
 // members under it are found by the uncompressed offsets of the member chain.
 //
-// Host path: the distinct members under a batch's windows are inflated once each (svx_inflate_raw_pair, two side by side)
+// Host path: the distinct members under a batch's windows are inflated once each (svx_bgzf.h's Inflater, two side by side)
 // on up to 16 threads, CRC32 and ISIZE checked; then the windows are gathered from the inflated members.  Batches are cut
 // into groups of at most kGroupMembers distinct members (in order of the windows' first member) so that a genome-wide call
 // never holds more than that many inflated members at once.  A few recent members stay cached for the short fetches that
@@ -19,7 +19,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
@@ -31,17 +30,13 @@
 #include <vector>
 
 #include "svx.h"
-#include "svx_bam.h"
+#include "svx_bgzf.h"
 #include "svx_fasta_bgzf.h"
-#include "svx_inflate_dev.h"
 #include "svx_text.h"
 
 namespace {
 
-inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-inline uint32_t le32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+using namespace svx_bgzf;  // Member, parse_member, Inflater, MemberTables
 
 constexpr uint32_t kGroupMembers = 4096;   // inflated members a host call holds at once (256 MiB)
 constexpr size_t kCacheMembers = 8;        // recent members kept between calls
@@ -57,42 +52,13 @@ bool host_only_env() {
     return off;
 }
 
-struct Member {
-    uint64_t coff, uoff;
-    uint32_t payload_off, payload_len, isize, crc;
-};
-
-// one member's header at coff: 0 ok, -1 malformed (BGZF: gzip magic, CM 8, FLG.FEXTRA, a BC subfield of length 2)
-int parse_member(const uint8_t* map, uint64_t fsize, uint64_t coff, Member* m, uint32_t* bsize) {
-    if (coff + 18 > fsize) return -1;
-    const uint8_t* p = map + coff;
-    if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || !(p[3] & 4)) return -1;
-    const uint32_t xlen = le16(p + 10);
-    if (coff + 12 + xlen > fsize) return -1;
-    uint32_t q = 12, end = 12 + xlen, bs = 0;
-    while (q + 4 <= end) {
-        const uint32_t slen = le16(p + q + 2);
-        if (p[q] == 66 && p[q + 1] == 67 && slen == 2 && q + 6 <= end) bs = (uint32_t)le16(p + q + 4) + 1;
-        q += 4 + slen;
-    }
-    if (!bs || bs < xlen + 20 || coff + bs > fsize) return -1;
-    m->coff = coff;
-    m->payload_off = 12 + xlen;
-    m->payload_len = bs - xlen - 20;
-    m->crc = le32(p + bs - 8);
-    m->isize = le32(p + bs - 4);
-    if (m->isize > 65536) return -1;
-    *bsize = bs;
-    return 0;
-}
-
 using Buf = std::shared_ptr<std::vector<uint8_t>>;
 
 struct Fz {
     const uint8_t* map = nullptr;
     uint64_t fsize = 0, total = 0;
     std::vector<Member> mem;        // the chain, in file order
-    std::vector<uint64_t> uoff;     // mem[i].uoff, for the searches
+    std::vector<uint64_t> coff, uoff;  // where member i starts in the file / in the uncompressed text
     mutable std::mutex mu;          // everything below
     std::string err;
     std::vector<std::pair<uint32_t, Buf>> cache;  // most recent last
@@ -144,27 +110,6 @@ std::string member_msg(const char* what, uint64_t coff) {
     char buf[160];
     snprintf(buf, sizeof buf, "%s BGZF member at compressed offset %llu", what, (unsigned long long)coff);
     return buf;
-}
-
-// member m inflated whole into out[isize]: its CRC32 and ISIZE checked
-bool inflate_member(const Fz* z, uint32_t m, uint8_t* out) {
-    const Member& M = z->mem[m];
-    uint64_t n_out = 0;
-    if (svx_inflate_raw(z->map + M.coff + M.payload_off, M.payload_len, out, M.isize, nullptr, 0, &n_out) != SVX_OK) return false;
-    return n_out == M.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), out, M.isize) == M.crc;
-}
-void inflate_two(const Fz* z, uint32_t ma, uint8_t* oa, uint32_t mb, uint8_t* ob, bool* ok_a, bool* ok_b) {
-    const Member &A = z->mem[ma], &B = z->mem[mb];
-    uint64_t na = 0, nb = 0;
-    int ra = SVX_E_INVALID, rb = SVX_E_INVALID;
-    if (svx_inflate_raw_pair(z->map + A.coff + A.payload_off, A.payload_len, oa, A.isize, ~0ull, &na, &ra,
-                             z->map + B.coff + B.payload_off, B.payload_len, ob, B.isize, ~0ull, &nb, &rb) != SVX_OK) {
-        *ok_a = inflate_member(z, ma, oa);  // (the pair call refused its arguments: each on its own, so that the
-        *ok_b = inflate_member(z, mb, ob);  //  damaged one is the one named)
-        return;
-    }
-    *ok_a = ra == SVX_OK && na == A.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), oa, A.isize) == A.crc;
-    *ok_b = rb == SVX_OK && nb == B.isize && (uint32_t)::crc32(::crc32(0L, Z_NULL, 0), ob, B.isize) == B.crc;
 }
 
 // the uncompressed byte range of bases [s, e) of sequence r (as fetch_one of svx_text.cpp computes it)
@@ -240,13 +185,12 @@ int z_open(const uint8_t* map, uint64_t size, const uint64_t* gzi_coff, const ui
                 ++gi;
             }
             Member m;
-            uint32_t bsize = 0;
-            if (parse_member(map, size, coff, &m, &bsize) != 0)
+            if (parse_member(map, size, coff, &m) != 0)
                 return fail(member_msg("truncated or malformed", coff) + " (not a complete BGZF file)");
-            m.uoff = u;
             z->mem.push_back(m);
+            z->coff.push_back(coff);
             z->uoff.push_back(u);
-            coff += bsize;
+            coff += m.bsize;
             u += m.isize;
         }
         // what is left may only be the end entry (end of the data)
@@ -324,20 +268,26 @@ int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t
         } catch (...) {
             return SVX_E_NOMEM;
         }
-        auto inflate_work = [&]() {
+        auto inflate_work = [&]() {  // two members at a time, each whole into its buffer; the first damaged one is named
+            Inflater inf[2] = {Inflater(false), Inflater(false)};  // (the build's own decoder whatever SVX_BAM_ZLIB says)
             for (;;) {
                 const size_t t = next.fetch_add(2);
                 if (t >= todo.size() || bad.load() >= 0) break;
-                const uint32_t ka = todo[t];
-                if (t + 1 < todo.size()) {
-                    const uint32_t kb = todo[t + 1];
-                    bool oa = false, ob = false;
-                    inflate_two(z, ms[ka], bufs[ka]->data(), ms[kb], bufs[kb]->data(), &oa, &ob);
-                    if (!oa) bad.store(ms[ka]);
-                    else if (!ob) bad.store(ms[kb]);
-                } else if (!inflate_member(z, ms[ka], bufs[ka]->data())) {
-                    bad.store(ms[ka]);
+                const size_t n = std::min<size_t>(2, todo.size() - t);
+                const uint8_t* in[2] = {nullptr, nullptr};
+                uint8_t* dst[2] = {nullptr, nullptr};
+                size_t in_len[2] = {0, 0}, isize[2] = {0, 0};
+                uint32_t crc[2] = {0, 0};
+                bool ok[2];
+                for (size_t k = 0; k < n; ++k) {
+                    const uint32_t m = ms[todo[t + k]];
+                    in[k] = z->map + z->coff[m] + z->mem[m].payload_off;
+                    in_len[k] = z->mem[m].payload_len;
+                    dst[k] = bufs[todo[t + k]]->data();
+                    isize[k] = z->mem[m].isize;
+                    crc[k] = z->mem[m].crc;
                 }
+                if (!Inflater::run_two(inf, in, in_len, dst, isize, isize, crc, n, ok)) bad.store(ms[todo[t + (ok[0] ? 1 : 0)]]);
             }
         };
         int rc = run_threads(todo.size() >= 8 ? n_threads : 1, inflate_work);
@@ -347,7 +297,7 @@ int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t
             z->stat[0] += todo.size();
         }
         if (bad.load() >= 0) {
-            z->set_err(member_msg("damaged or malformed", z->mem[(size_t)bad.load()].coff) + " (CRC32, ISIZE or DEFLATE stream)");
+            z->set_err(member_msg("damaged or malformed", z->coff[(size_t)bad.load()]) + " (CRC32, ISIZE or DEFLATE stream)");
             return SVX_E_INVALID;
         }
         // gather
@@ -364,10 +314,9 @@ int host_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64_t
                     uint64_t u = W.b0;
                     size_t k = (size_t)(std::lower_bound(ms.begin(), ms.end(), W.m0) - ms.begin());
                     for (uint32_t m = W.m0; m <= W.m1; ++m, ++k) {
-                        const Member& M = z->mem[m];
-                        const uint64_t hi = std::min<uint64_t>(W.b1, M.uoff + M.isize);
+                        const uint64_t hi = std::min<uint64_t>(W.b1, z->uoff[m] + z->mem[m].isize);
                         if (hi > u) {
-                            memcpy(raw.data() + (u - W.b0), bufs[k]->data() + (u - M.uoff), (size_t)(hi - u));
+                            memcpy(raw.data() + (u - W.b0), bufs[k]->data() + (u - z->uoff[m]), (size_t)(hi - u));
                             u = hi;
                         }
                     }
@@ -416,18 +365,18 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     if (!z->stream && hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) return broken();
     // the members not resident yet, and room for them in the arena
     std::vector<uint32_t> fresh;
-    uint64_t fresh_out = 0, in_bytes = 0;
+    MemberTables mt(z->arena_used);  // (mt.out_off[k]: the arena slot member fresh[k] will have)
     for (uint32_t m : ms) {
         if (z->slot[m] != ~0ull) continue;
         fresh.push_back(m);
-        fresh_out += ((uint64_t)z->mem[m].isize + 8 + 15) & ~15ull;
-        in_bytes += ((uint64_t)z->mem[m].payload_len + 3) & ~3ull;
+        mt.add(z->map, z->coff[m], z->mem[m]);
     }
+    const uint64_t in_bytes = mt.in_bytes;
     z->stat[3] += ms.size() - fresh.size();
-    if (z->arena_used + fresh_out > z->arena_cap) {
-        if (z->arena_used + fresh_out > kArenaCap) return 0;  // (past the cap: this call on the host)
+    if (mt.out_end > z->arena_cap) {
+        if (mt.out_end > kArenaCap) return 0;  // (past the cap: this call on the host)
         uint64_t cap = std::max<uint64_t>(64ull << 20, 2 * z->arena_cap);
-        while (cap < z->arena_used + fresh_out) cap *= 2;
+        while (cap < mt.out_end) cap *= 2;
         cap = std::min(cap, kArenaCap);
         void* p = nullptr;
         if (hipMalloc(&p, cap) != hipSuccess) return broken();
@@ -444,14 +393,6 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     }
     // the chunks of the gather: up to SVX_FASTA_CHUNK_BASES bases of a window inside two members
     std::vector<svx_fasta_chunk> chunks;
-    std::vector<uint64_t> new_slot(fresh.size());
-    {
-        uint64_t at = z->arena_used;
-        for (size_t k = 0; k < fresh.size(); ++k) {
-            new_slot[k] = at;
-            at += ((uint64_t)z->mem[fresh[k]].isize + 8 + 15) & ~15ull;
-        }
-    }
     bool unplanned = false;  // (a member neither resident nor staged: never, by construction — checked all the same)
     auto slot_of = [&](uint32_t m) -> uint64_t {
         if (z->slot[m] != ~0ull) return z->slot[m];
@@ -460,7 +401,7 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
             unplanned = true;
             return 0;
         }
-        return new_slot[k];
+        return mt.out_off[k];
     };
     for (const Win& w : wins) {
         const int32_t r = ref[w.i];
@@ -485,7 +426,7 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
             // member b only where the window reaches it (a member behind the window may be neither resident nor staged)
             const uint32_t nb = z->next_nonempty(ma);
             const uint32_t mb = nb <= w.m1 ? nb : (uint32_t)z->mem.size();
-            const uint64_t lim = mb < z->mem.size() ? z->mem[mb].uoff + z->mem[mb].isize : z->mem[ma].uoff + z->mem[ma].isize;
+            const uint64_t lim = mb < z->mem.size() ? z->uoff[mb] + z->mem[mb].isize : z->uoff[ma] + z->mem[ma].isize;
             const uint64_t rel = lim - off;  // bases in front of byte `lim`
             const uint64_t before = (rel / lw) * lb + std::min<uint64_t>(rel % lw, lb);
             const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(e, before) - s, SVX_FASTA_CHUNK_BASES);
@@ -496,9 +437,9 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
             c.off = off;
             c.s0 = s;
             c.src_a = slot_of(ma);
-            c.u_a = z->mem[ma].uoff;
+            c.u_a = z->uoff[ma];
             c.src_b = mb < z->mem.size() ? slot_of(mb) : c.src_a;
-            c.u_b = mb < z->mem.size() ? z->mem[mb].uoff : ~0ull;
+            c.u_b = mb < z->mem.size() ? z->uoff[mb] : ~0ull;
             c.magic = magic;
             c.shift = shift;
             c.n = (uint32_t)n;
@@ -510,13 +451,12 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
         }
     }
     if (unplanned) return 0;
-    // scratch: payloads | in_off | out_off (u64) | in_len | isize | crc | status | n_tok (u32) | chunks | packed output | tokens
+    // scratch: payloads | the member tables (MemberTables::write) | status | n_tok (u32) | chunks | packed output | tokens
     const uint32_t nf = (uint32_t)fresh.size();
     auto up256 = [](uint64_t x) { return (x + 255) & ~255ull; };
     const uint32_t arena_members = std::min<uint32_t>(nf, std::max<uint32_t>(1u, g_arena()));
     const uint64_t o_in = 0, o_tab = up256(in_bytes + 8);
-    const uint64_t tab_bytes = (uint64_t)nf * 16 + (uint64_t)nf * 12;
-    const uint64_t o_status = o_tab + up256(tab_bytes), o_ntok = o_status + up256((uint64_t)nf * 4);
+    const uint64_t o_status = o_tab + up256(mt.bytes()), o_ntok = o_status + up256((uint64_t)nf * 4);
     const uint64_t o_chunks = o_ntok + up256((uint64_t)nf * 4);
     const uint64_t o_tabs = o_chunks + up256(chunks.size() * sizeof(svx_fasta_chunk));  // (the oriented gather's two tables)
     const uint64_t o_packed = o_tabs + (tabs ? 512 : 0);
@@ -548,40 +488,17 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     }
     // stage: the payloads (by the threads), the tables, the chunks
     uint8_t* h = z->h_stage;
-    std::vector<uint64_t> in_off(nf);
-    {
-        uint64_t at = 0;
-        for (uint32_t k = 0; k < nf; ++k) {
-            in_off[k] = at;
-            at += ((uint64_t)z->mem[fresh[k]].payload_len + 3) & ~3ull;
-        }
-    }
     std::atomic<uint32_t> next(0);
     auto stage = [&]() {
         for (;;) {
             const uint32_t k0 = next.fetch_add(64);
             if (k0 >= nf) break;
-            for (uint32_t k = k0; k < std::min(nf, k0 + 64); ++k) {
-                const Member& M = z->mem[fresh[k]];
-                memcpy(h + o_in + in_off[k], z->map + M.coff + M.payload_off, M.payload_len);
-            }
+            for (uint32_t k = k0; k < std::min(nf, k0 + 64); ++k) memcpy(h + o_in + mt.in_off[k], mt.src[k], mt.in_len[k]);
         }
     };
     int rc = run_threads(nf >= 256 ? n_threads : 1, stage);
     if (rc != SVX_OK) return rc;
-    uint64_t* t_in_off = reinterpret_cast<uint64_t*>(h + o_tab);
-    uint64_t* t_out_off = t_in_off + nf;
-    uint32_t* t_in_len = reinterpret_cast<uint32_t*>(t_out_off + nf);
-    uint32_t* t_isize = t_in_len + nf;
-    uint32_t* t_crc = t_isize + nf;
-    for (uint32_t k = 0; k < nf; ++k) {
-        const Member& M = z->mem[fresh[k]];
-        t_in_off[k] = in_off[k];
-        t_out_off[k] = new_slot[k];
-        t_in_len[k] = M.payload_len;
-        t_isize[k] = M.isize;
-        t_crc[k] = M.crc;
-    }
+    mt.write(h + o_tab);
     if (!chunks.empty()) memcpy(h + o_chunks, chunks.data(), chunks.size() * sizeof(svx_fasta_chunk));
     if (tabs) {
         memset(h + o_chunks + chunks.size() * sizeof(svx_fasta_chunk), 0, o_tabs - o_chunks - chunks.size() * sizeof(svx_fasta_chunk));
@@ -591,9 +508,7 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     bool ok = hipMemcpyAsync(d, h, stage_need, hipMemcpyHostToDevice, z->stream) == hipSuccess;
     z->stat[2] += in_bytes;
     if (ok && nf)
-        ok = g_inflate(z->stream, d + o_in, reinterpret_cast<const uint64_t*>(d + o_tab), reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 16),
-                       reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 20), reinterpret_cast<const uint32_t*>(d + o_tab + (uint64_t)nf * 24), nf,
-                       z->d_arena, reinterpret_cast<const uint64_t*>(d + o_tab + (uint64_t)nf * 8), reinterpret_cast<uint32_t*>(d + o_status),
+        ok = mt.launch(g_inflate, z->stream, d + o_in, d + o_tab, 0, nf, z->d_arena, reinterpret_cast<uint32_t*>(d + o_status),
                        reinterpret_cast<uint32_t*>(d + o_ntok), d + o_tok, arena_members) == 0;
     if (tabs)
         ok = ok && g_gather_oriented(z->stream, z->d_arena, reinterpret_cast<const svx_fasta_chunk*>(d + o_chunks), (uint32_t)chunks.size(),
@@ -610,11 +525,11 @@ int device_fetch(Fz* z, const svx_fasta_geom* g, const int32_t* ref, const int64
     for (uint32_t k = 0; k < nf; ++k)
         if (status[k] != 0) {
             // nothing of this call becomes resident: the arena ends where it did
-            z->err = member_msg("damaged or malformed", z->mem[fresh[k]].coff) + " (CRC32, ISIZE or DEFLATE stream; device)";
+            z->err = member_msg("damaged or malformed", z->coff[fresh[k]]) + " (CRC32, ISIZE or DEFLATE stream; device)";
             return SVX_E_INVALID;
         }
-    for (uint32_t k = 0; k < nf; ++k) z->slot[fresh[k]] = new_slot[k];
-    if (nf) z->arena_used = new_slot[nf - 1] + (((uint64_t)z->mem[fresh[nf - 1]].isize + 8 + 15) & ~15ull);
+    for (uint32_t k = 0; k < nf; ++k) z->slot[fresh[k]] = mt.out_off[k];
+    z->arena_used = mt.out_end;
     z->stat[1] += nf;
     ++z->stat[4];
     if (out_bytes > out_lo) memcpy(out + out_lo, h + out_lo, out_bytes - out_lo);

@@ -1,4 +1,5 @@
-// svx_inflate_dev.h — what svx_bam.cpp (the device leg of the sequence slices) and svx_inflate.hip (the kernels) agree on.
+// svx_inflate_dev.h — what svx_bgzf.h (MemberTables: the members of a device inflate as the BAM reader's device leg and the
+// bgzip-FASTA handle lay them out; the callers size the token arena) and svx_inflate.hip (the kernels) agree on.
 #pragma once
 #include <stdint.h>
 
@@ -14,8 +15,8 @@
 #define SVX_INFLATE_ARENA_MEMBERS 20480u
 #endif
 
-// svx_bgzf_inflate_on_stream / svx_gather_ranges_on_stream (svx_inflate.hip), reached through pointers: svx_bam.cpp also
-// builds alone, without the kernels, for the CPU sanitizer tests.  hipError_t as int.
+// svx_bgzf_inflate_on_stream / svx_gather_ranges_on_stream (svx_inflate.hip), reached through pointers: the host files also
+// build alone, without the kernels, for the CPU sanitizer tests.  hipError_t as int.
 typedef int (*svx_inflate_launch_fn)(void* stream, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      const uint32_t* d_isize, const uint32_t* d_crc, uint32_t n_members, uint8_t* d_out,
                                      const uint64_t* d_out_off, uint32_t* d_status, uint32_t* d_n_tok, void* d_tok, uint32_t tok_members);

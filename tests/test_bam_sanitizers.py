@@ -25,7 +25,8 @@ def driver(request, tmp_path_factory):
     cmd = [gxx, "-std=c++17", "-g", "-O1", "-fsanitize=" + request.param, "-fno-sanitize-recover=all",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"),
            "-I", os.path.join(ROOT, "svim_asm_amd", "csrc"), os.path.join(ROOT, "tests", "native", "bam_sanitize.cpp"),
-           os.path.join(ROOT, "svim_asm_amd", "csrc", "svx_bam.cpp"), "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-lpthread",
+           os.path.join(ROOT, "svim_asm_amd", "csrc", "svx_bam.cpp"),
+           os.path.join(ROOT, "svim_asm_amd", "csrc", "svx_bgzf.cpp"), "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-lpthread",
            "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0:

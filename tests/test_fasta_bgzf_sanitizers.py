@@ -1,5 +1,5 @@
 """The host path of bgzip-compressed genomes (csrc/svx_fasta_bgzf.cpp behind svx_fasta_open_bgzf, with csrc/svx_text.cpp
-and the decoder of csrc/svx_bam.cpp) under AddressSanitizer + UBSan and, as a second build, ThreadSanitizer: random
+and the BGZF member layer of csrc/svx_bgzf.cpp) under AddressSanitizer + UBSan and, as a second build, ThreadSanitizer: random
 genomes bgzipped at random member sizes and levels, windows fetched by several caller threads on one handle, then
 damaged copies (flipped bytes, truncations, damaged .gzi columns).  Any out-of-bounds access, use after free, signed
 overflow, data race or leak fails the test, and so does a successful fetch whose bases differ from the text."""
@@ -22,7 +22,7 @@ def driver(request, tmp_path_factory):
     cmd = [gxx, "-std=c++17", "-g", "-O1", "-fsanitize=" + request.param, "-fno-sanitize-recover=all",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
            os.path.join(ROOT, "tests", "native", "fasta_bgzf_sanitize.cpp"), os.path.join(CSRC, "svx_text.cpp"),
-           os.path.join(CSRC, "svx_fasta_bgzf.cpp"), os.path.join(CSRC, "svx_bam.cpp"), "-L/opt/rocm/lib", "-lamdhip64",
+           os.path.join(CSRC, "svx_fasta_bgzf.cpp"), os.path.join(CSRC, "svx_bgzf.cpp"), "-L/opt/rocm/lib", "-lamdhip64",
            "-lz", "-lpthread", "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if res.returncode != 0:
