@@ -681,12 +681,21 @@ int svx_haplotype_distance_batch_mixed(svx_ctx* ctx, const uint8_t* pool, uint64
  * partition) are scipy's 1-based flat-cluster labels IN SCIPY'S ORDER — the reference takes the
  * coordinates of a paired call from cluster[0] (SVIM_COMBINE.py:184-363), so the order is part of the
  * result.  Distances are compared exactly as doubles (scipy's float64).  Partitions of one member get
- * label 1.  One lane per partition; any partition size is accepted.
+ * label 1.  Any partition size is accepted.
+ * Partitions of fewer than `group_min` members (svx_ctx_set_linkage_group_min) run one LANE each; larger ones, up to
+ * 2048 members, one WORKGROUP each: the same procedure with the nearest-neighbour search, the distance update and
+ * the sort of the merges spread over the group, on the full n x n matrix — in LDS up to SVX_LINKAGE_GROUP_LDS_N
+ * members, in the context workspace beyond.  Labels are identical on both.
  */
 int svx_linkage_cut_batch(svx_ctx* ctx, const double* dist, const uint32_t* n_members, uint32_t n_parts,
                           double cutoff, uint32_t* labels);
+#define SVX_LINKAGE_GROUP_LDS_N 128
+/* Smallest partition that takes the workgroup-per-partition kernel.  0 restores the default (16: the smallest size
+ * measured, from which on the group kernel is the faster one); 0xFFFFFFFF sends every partition down the lane path. */
+int svx_ctx_set_linkage_group_min(svx_ctx* ctx, uint32_t n);
 /* Asynchronous form: distances, member counts and labels in HBM; the HOST copy of n_members only sizes the scratch
- * of partitions too large for LDS (not read after the call returns).  No synchronisation. */
+ * of partitions too large for LDS and says which launches have work (not read after the call returns).  No
+ * synchronisation. */
 int svx_linkage_cut_batch_dev(svx_ctx* ctx, const double* d_dist, const uint32_t* n_members,
                               const uint32_t* d_n_members, uint32_t n_parts, double cutoff, uint32_t* d_labels);
 

@@ -146,6 +146,16 @@ typedef struct svx_vcf_in {
     const int64_t* b2_len;
     int sequence_alleles;     /* not options.symbolic_alleles */
     int read_names;           /* options.query_names */
+    /* ---- a cohort's merged records (optional; all NULL / 0 for a single sample's file).  Per candidate ROW:
+     * sample_text[sample_off[r] .. sample_off[r + 1]) replaces the genotype behind "GT\t" — the tab-joined genotypes
+     * of the S samples —, FORMAT is "GT" for every kind (no CN); info_text[info_off[r] .. info_off[r + 1]) is appended
+     * to INFO as it is (";NS=..;AC=..;AN=..").  Either may be given without the other. */
+    const char* sample_text;
+    const int64_t* sample_off;  /* n_rows + 1 */
+    uint64_t sample_bytes;
+    const char* info_text;
+    const int64_t* info_off;    /* n_rows + 1 */
+    uint64_t info_bytes;
 } svx_vcf_in;
 
 /* Formats into a buffer owned by the library: *text / *n_bytes (every line ends with '\n'); free with

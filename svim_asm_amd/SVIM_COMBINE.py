@@ -380,6 +380,88 @@ def _clock(stage, t0):
     return now
 
 
+def _job_distances(ctx, T, order, p_start, p_type, kstart, kend, job_a, job_b, job_p, job_two, threshold, reference, seq_split):
+    """Haplotype edit distances (compute_distance, :35-102) of the jobs (rows job_a, job_b of T, both members of partition
+    job_p): one reference window per partition with jobs, the recipes of the two haplotype strings, assembly and
+    alignment on the device.  job_two marks the jobs of two-member partitions, which only need "<= threshold?"; the
+    others get exact values.  PAIR (pair_tables) and the cohort merge (SVIM_MERGE.merge_tables) both come through here.
+    seq_split: where the second of two sequence pools starts in T.seqs (None: one pool).  float64 per job; "more
+    than the threshold" comes back as threshold + 1."""
+    n_parts = len(p_start)
+    s_sorted, e_sorted = kstart[order], kend[order]
+    seg_lo_all = np.minimum.reduceat(s_sorted, p_start)
+    seg_hi_all = np.maximum.reduceat(e_sorted, p_start)
+    # two-member partitions only need "<= threshold?"; larger ones get exact values so that the dendrogram
+    # above the cut (hence scipy's cluster label order) is the reference's.  Any threshold the reference
+    # accepts: a negative one pairs nothing, one beyond 32 bits everything
+    k_max = max(min(max(int(threshold), -1), 0xFFFFFFFE), 0)
+
+    def prepare(sel):
+        """Pool (one reference window per partition with jobs + the alleles behind them), recipes and thresholds of
+        the jobs `sel` (None: all)."""
+        ja, jb, jp, jtwo = (job_a, job_b, job_p, job_two) if sel is None else (job_a[sel], job_b[sel], job_p[sel], job_two[sel])
+        t0 = _clock_start()
+        # one reference window per partition with jobs: [min start - 100, max end + 100) of ALL its members (:45-46,...)
+        wp = np.unique(jp)
+        first_row = order[p_start[wp]]
+        p_contig = np.full(n_parts, -1, np.int64)
+        p_contig[wp] = T.key_contig()[first_row]
+        L_names = _reference_lengths(reference, T.contigs, p_contig[wp])
+        L_part = np.zeros(n_parts, np.int64)
+        L_part[wp] = L_names[p_contig[wp]]
+        wlo = np.maximum(0, seg_lo_all[wp] - 100)
+        whi = np.minimum(L_part[wp], seg_hi_all[wp] + 100)
+        t0 = _clock("pair_windows_plan_s", t0)
+        pool_w, off_w = _fetch_windows(reference, T.contigs, p_contig[wp], wlo, np.maximum(whi, wlo), False)
+        t0 = _clock("pair_windows_fetch_s", t0)
+        if not np.array_equal(off_w[1:] - off_w[:-1], np.maximum(whi - wlo, 0)):
+            raise ValueError("reference windows shorter than the index says")
+        win_base = np.zeros(n_parts + 1, np.int64)
+        win_base[wp] = off_w[:-1]
+        win_base[-1] = off_w[-1]
+        win_lo = np.zeros(n_parts, np.int64)
+        win_lo[wp] = wlo
+        pieces, extra = _haplotype_pieces(T, kstart, kend, ja, jb, jp, p_type, p_contig, win_base, win_lo, L_part, reference,
+                                          seq_split=seq_split)
+        pool = np.concatenate([pool_w] + extra) if extra else pool_w
+        # one call for both kinds of pairs (per-pair threshold; 0xFFFFFFFF = exact): one upload of the windows and
+        # alleles, one assembly of the haplotype strings, one wavefront pass and one bit-vector pass
+        per_pair = np.where(jtwo, np.uint32(k_max), np.uint32(0xFFFFFFFF)).astype(np.uint32)
+        _clock("pair_recipes_s", t0)
+        return pool, pieces.reshape(-1), per_pair
+
+    J = len(job_a)
+    n_chunks = 1 if J < _PAIR_CHUNK_MIN_JOBS else _PAIR_CHUNKS
+    if n_chunks == 1:
+        pool, pieces, per_pair = prepare(None)
+        tc = _clock_start()
+        dist = ctx.haplotype_distance_batch_mixed(pool, pieces, per_pair).astype(np.float64)
+        tc = _clock("pair_distances_s", tc)
+    else:
+        # a crowded sample (config 5: ~10^5 pairs): the jobs are cut into chunks of whole partitions and the device
+        # computes the distances of chunk i (one worker thread holds the context meanwhile; the call sleeps on a
+        # blocking event) while this thread fetches the windows and builds the recipes of chunk i + 1
+        from concurrent.futures import ThreadPoolExecutor
+        per_part = np.bincount(job_p, minlength=n_parts)
+        cuts = np.searchsorted(np.cumsum(per_part), J * np.arange(1, n_chunks) / n_chunks, side="left")
+        chunk_of = np.searchsorted(cuts, job_p, side="left")
+        dist = np.zeros(J, np.float64)
+        with ThreadPoolExecutor(max_workers=1) as worker:
+            pending = []
+            for c in range(n_chunks):
+                sel = np.flatnonzero(chunk_of == c)
+                if not len(sel):
+                    continue
+                pending.append((sel, worker.submit(ctx.haplotype_distance_batch_mixed, *prepare(sel))))
+            tc = _clock_start()
+            for sel, fut in pending:
+                dist[sel] = fut.result().astype(np.float64)
+            tc = _clock("pair_distances_wait_s", tc)
+    over = job_two & (dist == float(0xFFFFFFFF))
+    dist[over] = k_max + 1  # "more than the threshold" is all that is known, and all that matters
+    return dist
+
+
 def pair_tables(t1, t2, reference, bam, options, ctx=None):
     """pair_candidates on tables: the paired candidates as a CandidateTable, rows in the reference's order."""
     ctx = ctx or _lib.default_context(getattr(options, "device", 0) or 0)
@@ -444,77 +526,8 @@ def pair_tables(t1, t2, reference, bam, options, ctx=None):
     tc = _clock("pair_enumerate_s", tc)
     if classes and sum(len(a) for a in job_a):
         job_a, job_b, job_p, job_two = (np.concatenate(x) for x in (job_a, job_b, job_p, job_two))
-        s_sorted, e_sorted = kstart[order], kend[order]
-        seg_lo_all = np.minimum.reduceat(s_sorted, p_start)
-        seg_hi_all = np.maximum.reduceat(e_sorted, p_start)
-        # two-member partitions only need "<= threshold?"; larger ones get exact values so that the dendrogram
-        # above the cut (hence scipy's cluster label order) is the reference's.  Any threshold the reference
-        # accepts: a negative one pairs nothing, one beyond 32 bits everything
-        k_max = max(min(max(int(threshold), -1), 0xFFFFFFFE), 0)
-
-        def prepare(sel):
-            """Pool (one reference window per partition with jobs + the alleles behind them), recipes and thresholds of
-            the jobs `sel` (None: all)."""
-            ja, jb, jp, jtwo = (job_a, job_b, job_p, job_two) if sel is None else (job_a[sel], job_b[sel], job_p[sel], job_two[sel])
-            t0 = _clock_start()
-            # one reference window per partition with jobs: [min start - 100, max end + 100) of ALL its members (:45-46,...)
-            wp = np.unique(jp)
-            first_row = order[p_start[wp]]
-            p_contig = np.full(n_parts, -1, np.int64)
-            p_contig[wp] = T.key_contig()[first_row]
-            L_names = _reference_lengths(reference, T.contigs, p_contig[wp])
-            L_part = np.zeros(n_parts, np.int64)
-            L_part[wp] = L_names[p_contig[wp]]
-            wlo = np.maximum(0, seg_lo_all[wp] - 100)
-            whi = np.minimum(L_part[wp], seg_hi_all[wp] + 100)
-            t0 = _clock("pair_windows_plan_s", t0)
-            pool_w, off_w = _fetch_windows(reference, T.contigs, p_contig[wp], wlo, np.maximum(whi, wlo), False)
-            t0 = _clock("pair_windows_fetch_s", t0)
-            if not np.array_equal(off_w[1:] - off_w[:-1], np.maximum(whi - wlo, 0)):
-                raise ValueError("reference windows shorter than the index says")
-            win_base = np.zeros(n_parts + 1, np.int64)
-            win_base[wp] = off_w[:-1]
-            win_base[-1] = off_w[-1]
-            win_lo = np.zeros(n_parts, np.int64)
-            win_lo[wp] = wlo
-            pieces, extra = _haplotype_pieces(T, kstart, kend, ja, jb, jp, p_type, p_contig, win_base, win_lo, L_part, reference,
-                                              seq_split=t1.seqs_nbytes)
-            pool = np.concatenate([pool_w] + extra) if extra else pool_w
-            # one call for both kinds of pairs (per-pair threshold; 0xFFFFFFFF = exact): one upload of the windows and
-            # alleles, one assembly of the haplotype strings, one wavefront pass and one bit-vector pass
-            per_pair = np.where(jtwo, np.uint32(k_max), np.uint32(0xFFFFFFFF)).astype(np.uint32)
-            _clock("pair_recipes_s", t0)
-            return pool, pieces.reshape(-1), per_pair
-
-        J = len(job_a)
-        n_chunks = 1 if J < _PAIR_CHUNK_MIN_JOBS else _PAIR_CHUNKS
-        if n_chunks == 1:
-            pool, pieces, per_pair = prepare(None)
-            tc = _clock_start()
-            dist = ctx.haplotype_distance_batch_mixed(pool, pieces, per_pair).astype(np.float64)
-            tc = _clock("pair_distances_s", tc)
-        else:
-            # a crowded sample (config 5: ~10^5 pairs): the jobs are cut into chunks of whole partitions and the device
-            # computes the distances of chunk i (one worker thread holds the context meanwhile; the call sleeps on a
-            # blocking event) while this thread fetches the windows and builds the recipes of chunk i + 1
-            from concurrent.futures import ThreadPoolExecutor
-            per_part = np.bincount(job_p, minlength=n_parts)
-            cuts = np.searchsorted(np.cumsum(per_part), J * np.arange(1, n_chunks) / n_chunks, side="left")
-            chunk_of = np.searchsorted(cuts, job_p, side="left")
-            dist = np.zeros(J, np.float64)
-            with ThreadPoolExecutor(max_workers=1) as worker:
-                pending = []
-                for c in range(n_chunks):
-                    sel = np.flatnonzero(chunk_of == c)
-                    if not len(sel):
-                        continue
-                    pending.append((sel, worker.submit(ctx.haplotype_distance_batch_mixed, *prepare(sel))))
-                tc = _clock_start()
-                for sel, fut in pending:
-                    dist[sel] = fut.result().astype(np.float64)
-                tc = _clock("pair_distances_wait_s", tc)
-        over = job_two & (dist == float(0xFFFFFFFF))
-        dist[over] = k_max + 1  # "more than the threshold" is all that is known, and all that matters
+        dist = _job_distances(ctx, T, order, p_start, p_type, kstart, kend, job_a, job_b, job_p, job_two, threshold, reference,
+                              t1.seqs_nbytes)
         tc = _clock_start()
     # condensed distance vectors per size class (row-major pairs (i < j), :131-133), then the clusters
     at = 0
@@ -719,12 +732,14 @@ def _pool_of_strings(strings):
     return b"".join(enc), off
 
 
-def vcf_body(table, types_to_output, reference, options, sink=None, prefix=None):
+def vcf_body(table, types_to_output, reference, options, sink=None, prefix=None, cohort=None):
     """The record lines of write_final_vcf (:428-477) for the rows of `table` as bytes (every line ends with a
     newline): entries in the reference's list order, formatted, naturally sorted and numbered by
     svx_vcf_format.  With `sink` (a binary file object) the lines are written to it instead of being returned.
     With `prefix` (bytes): (address, length) of ONE buffer of the library's holding prefix + lines (svx_vcf_format_after;
-    release it with svx_vcf_free), or None when there are no lines."""
+    release it with svx_vcf_free), or None when there are no lines.
+    With `cohort` = ((sample pool, offsets), (INFO pool, offsets)), one slice per ROW of the table: a merged cohort's
+    records — the sample text behind FORMAT "GT", the INFO text appended, no CN (SVIM_MERGE.write_cohort_vcf)."""
     lib = _lib.load()
     t = table
     for k in [k for k in LAST_TIMING if k.startswith("vcf_")]:
@@ -814,6 +829,11 @@ def vcf_body(table, types_to_output, reference, options, sink=None, prefix=None)
         bases=ptr(bases, np.uint8), bases_bytes=len(bases), b_off=ptr(b_off, np.int64), b_len=ptr(b_len, np.int64),
         b2_off=ptr(b2_off, np.int64), b2_len=ptr(b2_len, np.int64), sequence_alleles=1 if seq else 0,
         read_names=1 if options.query_names else 0)
+    if cohort is not None:
+        (sample_pool, sample_off), (info_pool, info_off) = cohort
+        keep.extend([sample_pool, info_pool])
+        arg.sample_text, arg.sample_off, arg.sample_bytes = C.cast(C.c_char_p(sample_pool), C.c_void_p).value, ptr(sample_off, np.int64), len(sample_pool)
+        arg.info_text, arg.info_off, arg.info_bytes = C.cast(C.c_char_p(info_pool), C.c_void_p).value, ptr(info_off, np.int64), len(info_pool)
     text, n_bytes, n_lines = C.c_void_p(), C.c_uint64(), C.c_uint64()
     tc = _clock("vcf_prepare_s", tc)
     fd = None

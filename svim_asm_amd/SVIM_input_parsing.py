@@ -45,6 +45,8 @@ _OUTPUT = [
     ("--query_names", dict(action="store_true", help="Output names of supporting query sequences in INFO/READS")),
     ("--bgzip_output", dict(action="store_true", help="Write variants.vcf.gz (bgzip-compressed) and its tabix index "
                                                       "instead of variants.vcf")),
+    ("--keep_candidates", dict(action="store_true", help="Also write the final candidate table as candidates.svxt into the "
+                                                         "working directory: the input of svim-asm-merge")),
 ]
 
 

@@ -63,7 +63,9 @@ class VcfIn(C.Structure):
                 ("genotypes", C.c_void_p), ("genotype_off", C.c_void_p), ("n_genotypes", C.c_uint32),
                 ("n_entries", C.c_uint32), ("kind", C.c_void_p), ("row", C.c_void_p), ("bases", C.c_void_p),
                 ("bases_bytes", C.c_uint64), ("b_off", C.c_void_p), ("b_len", C.c_void_p), ("b2_off", C.c_void_p), ("b2_len", C.c_void_p),
-                ("sequence_alleles", C.c_int), ("read_names", C.c_int)]
+                ("sequence_alleles", C.c_int), ("read_names", C.c_int),
+                ("sample_text", C.c_void_p), ("sample_off", C.c_void_p), ("sample_bytes", C.c_uint64),
+                ("info_text", C.c_void_p), ("info_off", C.c_void_p), ("info_bytes", C.c_uint64)]
 
 
 VCF_DEL, VCF_INV, VCF_INS, VCF_DUPTAN_INS, VCF_DUPTAN_DUP, VCF_DUPINT_INS, VCF_DUPINT_DUP, VCF_BND, VCF_BND_REV = range(9)
@@ -110,6 +112,8 @@ SEG_DTYPE = np.dtype([("q_start", "<i4"), ("q_end", "<i4"), ("ref_id", "<i4"), (
                       ("ref_end", "<i4"), ("is_reverse", "<i4")])
 HAP_PIECE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("repeat", "<u2"), ("flags", "<u2")])  # svx_hap_piece
 PIECE_UPPER, PIECE_REVCOMP = 1, 2
+LINKAGE_GROUP_LDS_N = 128        # SVX_LINKAGE_GROUP_LDS_N: largest partition whose working matrix the group kernel keeps in LDS
+LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 RAW_DTYPE = np.dtype([("kind", "<i4"), ("a0", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("a3", "<i4"),
                       ("a4", "<i4"), ("a5", "<i4"), ("pad", "<i4")])
 
@@ -134,6 +138,7 @@ SYMBOLS = {
     "svx_ctx_barrier_timed_out": (C.c_int, [_P]),
     "svx_ctx_set_edit_wavefront_cap": (C.c_int, [_P, C.c_uint32]),
     "svx_ctx_set_pair_wait_free": (C.c_int, [_P, C.c_int]),
+    "svx_ctx_set_linkage_group_min": (C.c_int, [_P, C.c_uint32]),
     "svx_ctx_pair_retries": (C.c_int, [_P]),
     "svx_dev_malloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "svx_dev_free": (C.c_int, [_P, _P]),
@@ -343,6 +348,11 @@ class Context:
     def set_edit_wavefront_cap(self, max_edits):
         """Edits the wavefront pass of the edit distance resolves (0: bit-vector kernel only)."""
         self._check(self.lib.svx_ctx_set_edit_wavefront_cap(self.h, int(max_edits)))
+
+    def set_linkage_group_min(self, n):
+        """Smallest partition linkage_cut_batch clusters with one workgroup instead of one lane (0: the default;
+        LINKAGE_LANES_ONLY: none)."""
+        self._check(self.lib.svx_ctx_set_linkage_group_min(self.h, int(n)))
 
     # ---------------------------------------------------------------- device buffers
     def dev_array(self, host=None, nbytes=None):

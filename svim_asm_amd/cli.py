@@ -292,6 +292,9 @@ def _run_steps(options):
     types_to_output = [entry.strip() for entry in options.types.split(",")]
     write_vcf_table(sv_candidates, __version__, aln_file1.references, aln_file1.lengths, types_to_output, reference,
                     options, release_reference=False)  # (the process ends here: the kernel takes the mappings back)
+    if getattr(options, "keep_candidates", False):
+        from svim_asm_amd import SVIM_MERGE
+        SVIM_MERGE.keep_candidates(sv_candidates, options.working_dir)
     if _timeline.enabled():
         from svim_asm_amd import SVIM_COMBINE
         _timeline.mark("VCF written", stages={k: v for k, v in SVIM_COMBINE.LAST_TIMING.items() if k.startswith("vcf_")})

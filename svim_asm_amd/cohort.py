@@ -28,7 +28,15 @@ share that device); `--device` together with `--gpus` is an error.  Every child 
 started>, from which it takes its share of the node's CPUs (bamio.process_cpus: workers, reader threads and the device's
 share of the inflate work follow the CPUs per PROCESS).  A failed child does not stop the others; the parent's status is the
 worst of theirs; SIGINT / SIGTERM are passed on as SIGTERM and answered with 130 / 143 once every child is gone.  Processes
-started by hand set SVX_NODE_PROCESSES themselves."""
+started by hand set SVX_NODE_PROCESSES themselves.
+
+    svim-asm-cohort haploid|diploid MANIFEST GENOME --merge OUT_DIR [all other options]
+
+`--keep_candidates` leaves every sample's final table beside its VCF (working_dir/candidates.svxt); `--merge OUT_DIR` implies
+it and, once every sample has returned 0, merges the tables into OUT_DIR/cohort.vcf with one genotype column per sample
+(svim-asm-merge, SVIM_MERGE.py): in this process on its default context, or — with `--gpus N` — in one more fresh child on the
+first listed device, started when all children have exited with 0; its status counts towards the parent's.  If a sample
+failed, no merge is attempted."""
 import gc
 import logging
 import os
@@ -197,6 +205,9 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
         _timeline.mark("PAIR done", sample=first_no + k)
         write_vcf_table(candidates, cli.__version__, mine_files[0].references, mine_files[0].lengths,
                         [entry.strip() for entry in o.types.split(",")], reference, o, ctx=ctx)
+        if getattr(o, "keep_candidates", False):
+            from svim_asm_amd import SVIM_MERGE
+            SVIM_MERGE.keep_candidates(candidates, wd)
         _timeline.mark("VCF written", sample=first_no + k)
         logging.info("sample %d of %d: %s/variants.vcf%s", first_no + k + 1, n_total, wd, ".gz" if getattr(o, "bgzip_output", False) else "")
     for f in files:
@@ -225,6 +236,39 @@ def _entry_script():
 def _child_command(mode, share, genome, device, rest):
     """argv of one child: today's single-process command on its share of the manifest (the seam a test replaces)."""
     return [sys.executable, _entry_script(), mode, share, genome, "--device", str(device)] + list(rest)
+
+
+def _take_merge(rest):
+    """(rest with --keep_candidates once and without --merge, OUT_DIR or None)."""
+    rest, out_dir = _take_option(rest, "--merge", None, convert=str)
+    if out_dir is not None and "--keep_candidates" not in rest:
+        rest = list(rest) + ["--keep_candidates"]
+    return rest, out_dir
+
+
+def _merge_command(mode, out_dir, genome, sample_dirs, device, rest):
+    """argv of the merge child of `--gpus N --merge OUT_DIR`: svim-asm-merge with the options of `rest` it shares with
+    the samples' command (a seam like _child_command)."""
+    for name in ("--cohort_workers", "--cohort_group", "--cohort_threads", "--cohort_lanes"):  # (this command's own)
+        rest, _ = _take_option(rest, name, 0)
+    o = parse_arguments(cli.__version__, [mode, out_dir] + ["-"] * (2 if mode == "diploid" else 1) + [genome] + list(rest))
+    script = os.path.join(os.path.dirname(_entry_script()), "svim-asm-merge")
+    return [sys.executable, script, out_dir, genome] + list(sample_dirs) + ["--device", str(device)] + _merge_options(o)
+
+
+def _merge_options(o):
+    """The options svim-asm-merge shares with the samples' command, as its argument list."""
+    if getattr(o, "query_names", False):
+        logging.info("MERGE: --query_names is ignored, read names are not carried into the merged file")
+    out = ["--types", o.types]
+    for name in ("partition_max_distance", "max_edit_distance"):
+        if getattr(o, name, None) is not None:
+            out += ["--" + name, str(getattr(o, name))]
+    for flag in ("symbolic_alleles", "tandem_duplications_as_insertions", "interspersed_duplications_as_insertions", "bgzip_output",
+                 "verbose"):
+        if getattr(o, flag, False):
+            out.append("--" + flag)
+    return out
 
 
 def _names_device(rest):
@@ -272,6 +316,7 @@ def launch(mode, manifest, genome, rest):
     if rest is None:
         print("svim-asm-cohort: " + devices, file=sys.stderr)
         return 2
+    rest, merge_dir = _take_merge(rest)  # (the children keep their tables; the merge is one more child, below)
     samples = read_manifest(manifest, 2 if mode == "diploid" else 1)  # (a malformed manifest fails here, before any child exists)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
     shares = [(devices[k], share) for k, share in enumerate(deal(samples, len(devices))) if share]
@@ -288,6 +333,19 @@ def launch(mode, manifest, genome, rest):
 
     handled = (signal.SIGINT, signal.SIGTERM) if threading.current_thread() is threading.main_thread() else ()
     before = {s: signal.signal(s, stop_children) for s in handled}
+
+    def wait_for_children():
+        deadline = None
+        while any(p.poll() is None for p in procs):
+            if caught and deadline is None:
+                deadline = time.monotonic() + 10.0
+            if deadline is not None and time.monotonic() > deadline:
+                for p in procs:  # (a child that does not answer SIGTERM: nothing may outlive the parent)
+                    if p.poll() is None:
+                        p.kill()
+            time.sleep(0.02)
+
+    merge_proc = None
     try:
         for k, (device, share) in enumerate(shares):
             if caught:
@@ -298,15 +356,16 @@ def launch(mode, manifest, genome, rest):
             procs.append(subprocess.Popen(_child_command(mode, path, genome, device, rest), env=env))
             if caught:  # (a signal that arrived while this child was being started has not reached it)
                 stop_children()
-        deadline = None
-        while any(p.poll() is None for p in procs):
-            if caught and deadline is None:
-                deadline = time.monotonic() + 10.0
-            if deadline is not None and time.monotonic() > deadline:
-                for p in procs:  # (a child that does not answer SIGTERM: nothing may outlive the parent)
-                    if p.poll() is None:
-                        p.kill()
-            time.sleep(0.02)
+        wait_for_children()
+        if merge_dir is not None and not caught:
+            if len(procs) == len(shares) and all(p.returncode == 0 for p in procs):
+                # one more fresh child, alone on the first listed device: this process still never touches the GPU
+                merge_proc = subprocess.Popen(_merge_command(mode, merge_dir, genome, [wd for wd, _ in samples], devices[0], rest),
+                                              env=dict(os.environ, SVX_NODE_PROCESSES="1"))
+                procs.append(merge_proc)
+                wait_for_children()
+            else:
+                logging.info("MERGE: not attempted, a sample failed")
     finally:
         for p in procs:
             if p.poll() is None:  # (an exception on the way: the same promise)
@@ -319,6 +378,11 @@ def launch(mode, manifest, genome, rest):
     for p, (device, share) in zip(procs, shares):
         rc = p.returncode
         logging.info("CHILD: device %d, %d sample(s), %s", device, len(share),
+                     "status %d" % rc if rc >= 0 else "killed by signal %d" % -rc)
+        worst = max(worst, rc if rc >= 0 else 128 - rc)
+    if merge_proc is not None:
+        rc = merge_proc.returncode
+        logging.info("MERGE: device %d, %d sample(s), %s", devices[0], len(samples),
                      "status %d" % rc if rc >= 0 else "killed by signal %d" % -rc)
         worst = max(worst, rc if rc >= 0 else 128 - rc)
     if caught:
@@ -344,6 +408,7 @@ def main(argv=None):
     rest, per_group = _take_option(rest, "--cohort_group", 1)
     rest, reader_threads = _take_option(rest, "--cohort_threads", 0)
     rest, lanes = _take_option(rest, "--cohort_lanes", 0)
+    rest, merge_dir = _take_merge(rest)
     samples = read_manifest(manifest, n_bams)
     _timeline.mark("cohort main")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
@@ -413,6 +478,13 @@ def main(argv=None):
     _timeline.dump()
     if state["error"] is not None:
         raise state["error"]
+    if merge_dir is not None:
+        if state["rc"]:
+            logging.info("MERGE: not attempted, a sample failed")
+        else:
+            # the workers have joined and every sample returned 0: here, on the process's default context
+            from svim_asm_amd import merge_cli
+            return merge_cli.main([merge_dir, genome] + [wd for wd, _ in samples] + ["--device", str(device)] + _merge_options(opts[0]))
     return state["rc"]
 
 

@@ -43,6 +43,7 @@ struct svx_ctx {
     uint32_t pair_single_max = 131072;  // svx_ctx_set_pair_single_launch_max: largest batch of the one-launch pair sort
     uint64_t small_batch_ops = 1ull << 23;  // svx_ctx_set_small_batch_ops: largest batch of the two-launch CIGAR path
     bool split_chain = false;               // svx_ctx_set_split_chain: the split-segment chain as three launches
+    uint32_t link_group_min = 0;            // svx_ctx_set_linkage_group_min: smallest partition of the group kernel (0: default)
     char err[512] = {0};
 };
 

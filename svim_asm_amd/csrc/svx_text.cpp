@@ -392,6 +392,12 @@ int vcf_format_impl(const svx_vcf_in* in, char** text, int fd, uint64_t file_at,
             if (in->sequence_alleles && k == SVX_VCF_DUPTAN_INS && in->copies[r] > 0 &&
                 (uint64_t)in->b_len[e] * ((uint64_t)in->copies[r] + 1) > (1ull << 31))
                 return SVX_E_TOO_LARGE;  // ALT = REF x (copies + 1) (:209-214): a line of more than 2 GiB is a damaged input
+            if (in->sample_text && (!in->sample_off || in->sample_off[r] < 0 || in->sample_off[r + 1] < in->sample_off[r] ||
+                                    (uint64_t)in->sample_off[r + 1] > in->sample_bytes))
+                return SVX_E_INVALID;
+            if (in->info_text && (!in->info_off || in->info_off[r] < 0 || in->info_off[r + 1] < in->info_off[r] ||
+                                  (uint64_t)in->info_off[r + 1] > in->info_bytes))
+                return SVX_E_INVALID;
             if (in->read_names) {
                 if (in->r_off[r] < 0 || in->r_off[r + 1] < in->r_off[r]) return SVX_E_INVALID;
                 for (int64_t j = in->r_off[r]; j < in->r_off[r + 1]; ++j)
@@ -570,8 +576,12 @@ int vcf_format_impl(const svx_vcf_in* in, char** text, int fd, uint64_t file_at,
                     pool_str(o, in->names, in->name_off, in->r_flat[j]);
                 }
             }
+            if (in->info_text) o.bytes(reinterpret_cast<const uint8_t*>(in->info_text) + in->info_off[r], (size_t)(in->info_off[r + 1] - in->info_off[r]));
             // FORMAT sample
-            if (k == SVX_VCF_DUPTAN_DUP) {
+            if (in->sample_text) {  // a cohort's record: one genotype per sample, no CN
+                o.lit("\tGT\t");
+                o.bytes(reinterpret_cast<const uint8_t*>(in->sample_text) + in->sample_off[r], (size_t)(in->sample_off[r + 1] - in->sample_off[r]));
+            } else if (k == SVX_VCF_DUPTAN_DUP) {
                 o.lit("\tGT:CN\t");
                 pool_str(o, in->genotypes, in->genotype_off, in->gt[r]);
                 o.ch(':');
