@@ -55,6 +55,9 @@ def edit_distance(a, b):
     return int(prev[-1])
 
 
+_textbook_edit_distance = edit_distance
+
+
 def haplotypes(c1, c2, seqs):
     """The two strings compute_distance aligns."""
     def up(contig, start, end):
@@ -86,18 +89,25 @@ def haplotypes(c1, c2, seqs):
     return out
 
 
-def distance(c1, c2, seqs):
+def distance(c1, c2, seqs, edit_distance=None):
+    """edit_distance: a callable on two byte strings (the compiled full DP of the oracle, say) in place of the textbook
+    one above, which it must equal (tests/test_merge_host.py pins that)."""
     if c1.type == "BND":
         if c1.source_direction == c2.source_direction and c1.dest_direction == c2.dest_direction:
             return (abs(c1.source_start - c2.source_start) + abs(c1.dest_start - c2.dest_start)) / 3000
         return 99999
-    return edit_distance(*haplotypes(c1, c2, seqs))
+    a, b = haplotypes(c1, c2, seqs)
+    if edit_distance is None:
+        return _textbook_edit_distance(a, b)
+    return int(edit_distance(a.encode("latin-1"), b.encode("latin-1")))
 
 
-def merge(samples, seqs, partition_max_distance=1000, max_edit_distance=200, merge_max_partition=1024):
+def merge(samples, seqs, partition_max_distance=1000, max_edit_distance=200, merge_max_partition=1024, edit_distance=None,
+          record=None):
     """samples: one list of Candidate objects per sample, each with its single-sample genotype.
     Returns ([(allele_key of the representative, [genotype text per sample])] in record order, number of partitions left
-    unclustered)."""
+    unclustered).  record: a list that receives, per clustered partition, (type, [allele keys in partition order],
+    condensed distance vector)."""
     S = len(samples)
     # ---- collapse: a dictionary; a distinct allele remembers its first carrier and all carriers
     alleles = {}
@@ -127,7 +137,10 @@ def merge(samples, seqs, partition_max_distance=1000, max_edit_distance=200, mer
                 unclustered += 1
             else:
                 from scipy.cluster.hierarchy import fcluster, linkage
-                cond = [float(distance(part[i]["obj"], part[j]["obj"], seqs)) for i in range(n - 1) for j in range(i + 1, n)]
+                cond = [float(distance(part[i]["obj"], part[j]["obj"], seqs, edit_distance))
+                        for i in range(n - 1) for j in range(i + 1, n)]
+                if record is not None:
+                    record.append((typ, [allele_key(a["obj"]) for a in part], cond))
                 cut = 0.3 if typ == "BND" else max_edit_distance
                 labels = fcluster(linkage(np.array(cond), method="complete"), cut, criterion="distance").tolist()
             for label in sorted(set(labels)):

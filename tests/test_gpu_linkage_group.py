@@ -3,7 +3,13 @@
 Every batch is clustered twice, with set_linkage_group_min(2) — every partition of two or more members on the group
 kernel — and with set_linkage_group_min(LINKAGE_LANES_ONLY) — the lane path, which is all there was before —; the
 labels must be equal between the two and equal to scipy's fcluster(linkage(y, "complete"), t, "distance").
-Edit distances tie constantly, so four of the five distance families are made of ties."""
+Edit distances tie constantly, so four of the five distance families are made of ties.
+
+The kernel's last size class (513 ... 2048 members, matrix in the workspace) is held to scipy alone — a lane needs
+seconds at these sizes —: 512 | 513, the product's cap of 1024, 2047 | 2048, and 2049, the first size the group kernel
+hands back to the lanes.  One more batch mixes everything that shares the call's scratch buffer at the default
+threshold: lane partitions on HBM scratch (11-15 members) between group partitions with their matrix in LDS and in
+the workspace, the offsets computed by the host entry (plan_add) and by the device entry (k_linkage_offsets)."""
 import functools
 
 import numpy as np
@@ -124,3 +130,51 @@ def test_single_members_and_empty_batches(svx_ctx, group_min):
         assert svx_ctx.lib.svx_linkage_cut_batch_dev(svx_ctx.h, None, None, None, 0, 0.3, None) == 0
         ones = np.ones(3, np.uint32)
         assert _run_dev(svx_ctx, np.zeros(1), ones, 0.3) == [1, 1, 1]
+
+
+# ------------------------------------------------------------------------------ the last size class, against scipy alone
+BIG = [512, 513, 1024, 2047, 2048]
+
+
+def _big_batch(n):
+    """The five families at n members, single members and a few partitions of 3 between them."""
+    parts = []
+    for family in FAMILIES:
+        parts += [(family, n), ("equal", 1), (family, 3)]
+    counts = np.array([m for _, m in parts], np.uint32)
+    dist = np.concatenate([_condensed(f, m) for f, m in parts if m > 1])
+    return parts, counts, dist
+
+
+@pytest.mark.parametrize("n", BIG)
+def test_last_size_class_equals_scipy_on_both_entries(svx_ctx, group_min, n):
+    parts, counts, dist = _big_batch(n)
+    group_min(2)
+    for cutoff in CUTOFFS:
+        want = _expected(parts, cutoff)
+        assert svx_ctx.linkage_cut_batch(dist, counts, cutoff).tolist() == want
+        assert _run_dev(svx_ctx, dist, counts, cutoff) == want
+
+
+def test_first_size_handed_back_to_the_lanes(svx_ctx):
+    """2049 members beside 2048 and 16 at the default settings: the group kernel's largest size and the lane path's
+    HBM scratch slice in one call.  (The 2049-member lane takes seconds: one family, one cut-off.)"""
+    parts = [("int4", 2048), ("int4", 16), ("int4", 2049)]
+    counts = np.array([m for _, m in parts], np.uint32)
+    dist = np.concatenate([_condensed(f, m) for f, m in parts])
+    assert svx_ctx.linkage_cut_batch(dist, counts, 2.0).tolist() == _expected(parts, 2.0)
+
+
+def test_lane_scratch_and_group_matrices_share_one_buffer(svx_ctx):
+    """Default threshold (16): 11-15 members are lanes on HBM scratch, 129 and more are group partitions with their
+    matrix in the same buffer, 1 takes nothing.  Both entries; then the device entry again behind 300 partitions of two
+    and three members, so that k_linkage_offsets (256 threads) walks chunks of two partitions."""
+    sizes = [11, 300, 13, 129, 15, 513, 12, 1, 1024, 14]
+    parts = [(FAMILIES[i % len(FAMILIES)], n) for i, n in enumerate(sizes)]
+    front = [(FAMILIES[i % len(FAMILIES)], 2 + i % 2) for i in range(300)]
+    for batch in (parts, front + parts):
+        counts = np.array([m for _, m in batch], np.uint32)
+        dist = np.concatenate([_condensed(f, m) for f, m in batch if m > 1])
+        want = _expected(batch, 2.0)
+        assert _run_dev(svx_ctx, dist, counts, 2.0) == want
+        assert svx_ctx.linkage_cut_batch(dist, counts, 2.0).tolist() == want

@@ -1,6 +1,9 @@
 """The cohort merge (svim_asm_amd/SVIM_MERGE.py) where there is no GPU: the kernels answered by the oracle
 (tests/helpers.OracleBackedContext), every merged table and genotype matrix held against the plain-Python restatement
-(tests/merge_restatement.py); the multi-sample VCF writer; --keep_candidates."""
+(tests/merge_restatement.py); the multi-sample VCF writer; --keep_candidates.  The cohort-sized partitions of
+tests/merge_cases.py: every type at 11, 17 and 33 distinct alleles, the cohort with every type and partition size at
+once, the chunked distance path, and the condensed vectors handed to the linkage call; the cases that only run on the
+device (tests/test_gpu_merge.py) are held to their non-triviality condition here."""
 import gzip
 import logging
 import os
@@ -11,7 +14,7 @@ import pytest
 from svim_asm_amd import SVCandidate, SVIM_COMBINE, SVIM_MERGE
 from svim_asm_amd.fasta import FastaFile
 from svim_asm_amd.table import CandidateTable
-from tests import helpers, merge_restatement as R, tabix_reader
+from tests import helpers, merge_cases as M, merge_restatement as R, tabix_reader
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config1")
 REF = os.path.join(GOLD, "ref.fa")
@@ -153,6 +156,111 @@ def test_contig_mismatch_is_refused():
 def test_empty_samples():
     assert both([[], [], [], []]) == []
     assert both([[], [DEL(5000)], [], []]) == [(("DEL", "chr1", 5000, 5050), ["./.", "1/1", "./.", "./."])]
+
+
+# ------------------------------------------------------------------------------ cohort-sized partitions
+def test_the_compiled_edit_distances_equal_the_textbook_one():
+    """The large cases' expected answers use the oracle's C full DP (and, for the wide cohort, its band-doubling DP) in
+    place of the restatement's textbook rows: the three agree on haplotype pairs of every type from the builders."""
+    from oracle import orc
+    pairs = []
+    for typ in ("DEL", "INS", "INV", "DUP_TAN", "DUP_INT"):
+        objs = [make("1/1") for make in M.BUILDERS[typ](33)]
+        pairs += [R.haplotypes(objs[i], objs[j], SEQS) for i, j in ((0, 1), (0, 32), (3, 17), (5, 6), (9, 30), (11, 12), (16, 31),
+                                                                   (20, 21), (2, 29), (7, 25), (13, 14), (18, 27), (4, 4))]
+    assert len(pairs) >= 60 and 600 < max(len(a) for a, _ in pairs) <= 700
+    assert any(a != a.upper() for a, _ in pairs) and any("N" in a for a, _ in pairs)  # inserted bytes keep their case
+    for a, b in pairs:
+        d = R.edit_distance(a, b)
+        assert orc.edit_distance(a.encode("latin-1"), b.encode("latin-1")) == d
+        assert orc.edit_distance_banded(a.encode("latin-1"), b.encode("latin-1")) == d
+    assert len({R.edit_distance(a, b) for a, b in pairs}) > 20
+
+
+@pytest.mark.parametrize("n", [11, 17, 33])
+@pytest.mark.parametrize("typ", M.TYPES)
+def test_one_partition_of_every_type_beyond_ten_members(typ, n):
+    assert M.is_non_trivial((typ, n))
+    got, proxy = M.check((typ, n), helpers.OracleBackedContext())
+    assert [sizes.tolist() for _, sizes, _ in proxy.linkage] == [[n]]
+    assert proxy.distance_jobs == ([] if typ == "BND" else [n * (n - 1) // 2])
+
+
+DEVICE_ONLY = [("DEL", 65), ("DEL", 128), ("DEL", 129), ("INS", 65), ("INS", 129), ("BND", 129), "wide"]
+
+
+@pytest.mark.parametrize("case", DEVICE_ONLY, ids=str)
+def test_the_cases_that_only_run_on_the_device_are_non_trivial(case):
+    """tests/test_gpu_merge.py runs these against the restatement; here only the condition on the inputs: at the case's
+    max_edit_distance the restatement makes more than one and fewer than n records and a cluster of three or more."""
+    assert M.is_non_trivial(case)
+    (typ, keys, cond), = M.expected(case)[1]
+    assert len(keys) == (17 if case == "wide" else case[1])
+    if typ == "BND":  # span-position distances on either side of 0.3 beside the direction-mismatch sentinel
+        assert any(d < 0.3 for d in cond) and any(0.3 < d < 1 for d in cond) and 99999.0 in cond
+    if case == "wide":
+        a, b = R.haplotypes(DEL(100000, 40), DEL(100000 + 16 * 600, 40), SEQS)
+        assert len(a) > 9500
+
+
+def test_every_type_and_partition_size_in_one_call():
+    assert M.is_non_trivial("everything")
+    got, proxy = M.check("everything", helpers.OracleBackedContext())
+    assert len({k[0] for k, _ in got}) == 6
+    (_, edit_sizes, _), (_, bnd_sizes, cut) = proxy.linkage
+    assert sorted(edit_sizes.tolist() + bnd_sizes.tolist()) == sorted(n for _, sizes in M.EVERYTHING for n in sizes if n > 1)
+    assert cut == 0.3 and {10, 11, 15, 16, 17, 33, 65, 129} <= set(edit_sizes.tolist())
+    # a fifth of the alleles is carried by more than one sample
+    assert sum(sum(g != "./." for g in row) > 1 for _, row in got) >= 10
+
+
+def _non_empty_chunks(jobs_per_partition, n_chunks):
+    """Chunks of whole partitions: chunk boundary c (of n_chunks - 1) lies behind the first partition at which the
+    running job count reaches c / n_chunks of all jobs; a partition belongs to the chunk numbered by the boundaries
+    before it."""
+    total, running, boundary = sum(jobs_per_partition), 0, {}
+    for p, jobs in enumerate(jobs_per_partition):
+        running += jobs
+        for c in range(1, n_chunks):
+            if c not in boundary and running * n_chunks >= total * c:
+                boundary[c] = p
+    return {sum(boundary[c] < p for c in range(1, n_chunks)) for p in range(len(jobs_per_partition))}
+
+
+def test_chunked_distance_jobs_of_a_dominant_partition(monkeypatch):
+    """SVIM_COMBINE._job_distances in chunks (as for 30 000 jobs or more), one partition holding most of the jobs: the
+    answer is the one-chunk answer and the restatement's, also where a chunk comes out empty."""
+    assert M.is_non_trivial("chunks")
+    one, proxy = M.check("chunks", helpers.OracleBackedContext())
+    jobs = [len(cond) for _, _, cond in M.expected("chunks")[1]]
+    assert proxy.distance_jobs == [sum(jobs)] and max(jobs) == 33 * 32 // 2 and len(jobs) == 13
+    monkeypatch.setattr(SVIM_COMBINE, "_PAIR_CHUNK_MIN_JOBS", 1)
+    empty = []
+    for n_chunks in (2, 3, 8):
+        monkeypatch.setattr(SVIM_COMBINE, "_PAIR_CHUNKS", n_chunks)
+        got, proxy = M.check("chunks", helpers.OracleBackedContext())
+        assert got == one
+        filled = _non_empty_chunks(jobs, n_chunks)
+        assert len(proxy.distance_jobs) == len(filled) > 1 and sum(proxy.distance_jobs) == sum(jobs)
+        empty.append(n_chunks - len(filled))
+    assert max(empty) > 0
+
+
+class _OffByOne(helpers.OracleBackedContext):
+    """One exact distance well above the cut comes back one too large."""
+
+    def haplotype_distance_batch_mixed(self, pool, pieces, k_max):
+        out = helpers.OracleBackedContext.haplotype_distance_batch_mixed(self, pool, pieces, k_max)
+        out[int(np.argmax(out))] += 1
+        return out
+
+
+def test_a_distance_wrong_by_one_fails_on_the_vectors_where_the_records_survive():
+    case = ("DEL", 17)
+    got, proxy = M.run(case, _OffByOne())
+    assert got == M.expected(case)[0]  # the largest distance lies above the cut: the flat clusters do not move
+    with pytest.raises(AssertionError):
+        M.check(case, _OffByOne())
 
 
 # ------------------------------------------------------------------------------ the writer
