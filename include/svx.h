@@ -65,6 +65,22 @@ int svx_device_count(void);
  * process per GPU of a node (svim-asm-cohort --device k).  `len` >= 16. */
 int svx_device_pci_bus_id(int device, char* out, int len);
 
+/* THE SCRATCH CONTRACT.  Every entry point that takes a context carves its scratch out of two long-lived HBM regions
+ * of that context (a workspace and a staging region; svx_collect_batch also a page-locked host block).  A region is
+ * reallocated only when a call needs more than it has, and nothing outside the first 4 KiB of the workspace (a header
+ * of counters that the kernels using them leave as they found them, see DESIGN.md "Scratch contract") is ever cleared:
+ * THE CONTENTS OF CONTEXT SCRATCH BETWEEN CALLS ARE UNSPECIFIED.  A call sees what the previous call — of any entry
+ * point, of any size — left there, and must write every scratch word before it reads it.
+ *
+ * The two entries below are a TEST FACILITY for that contract; no product path calls them and neither launches a
+ * kernel.  svx_ctx_scratch_fill waits for the context's stream, sets every byte of the workspace behind the header,
+ * every byte of the staging region and every byte of the host block to `byte` (low 8 bits; hipMemset / memset), and
+ * waits again.  A region that is not allocated yet is skipped; the header, a pending check of a wait between
+ * workgroups and everything the caller owns stay as they are.  svx_ctx_scratch_header waits for the stream and copies
+ * the 1024 words of the header to `out` (zeros while there is no workspace). */
+int svx_ctx_scratch_fill(svx_ctx* ctx, int byte);
+int svx_ctx_scratch_header(svx_ctx* ctx, uint32_t out[1024]);
+
 /* svx_cigar_extract* run batches of at most `max_ops` CIGAR ops in TWO kernel launches (tiles of 1024
  * ops; every workgroup of the second kernel scans all tile descriptors itself): the operating point of
  * the svim-asm CLI — one BAM of an assembly (~1.5 M ops) or both haplotype BAMs of a diploid sample

@@ -127,6 +127,8 @@ SYMBOLS = {
     "svx_last_error": (C.c_char_p, [_P]),
     "svx_version": (C.c_char_p, []),
     "svx_device_count": (C.c_int, []),
+    "svx_ctx_scratch_fill": (C.c_int, [_P, C.c_int]),
+    "svx_ctx_scratch_header": (C.c_int, [_P, _P]),
     "svx_ctx_set_small_batch_ops": (C.c_int, [_P, C.c_uint64]),
     "svx_bgzf_inflate_dev": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "svx_hbm_read_probe_dev": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
@@ -320,6 +322,17 @@ class Context:
 
     def sync(self):
         self._check(self.lib.svx_ctx_sync(self.h))
+
+    def scratch_fill(self, byte):
+        """Test facility: every byte of the context's scratch (workspace behind its 4 KiB header, staging region,
+        page-locked block) set to `byte` — the contents of scratch between calls are unspecified (include/svx.h)."""
+        self._check(self.lib.svx_ctx_scratch_fill(self.h, int(byte) & 0xFF))
+
+    def scratch_header(self):
+        """Test facility: the 1024 words of the workspace header (zeros while there is no workspace)."""
+        out = np.zeros(1024, np.uint32)
+        self._check(self.lib.svx_ctx_scratch_header(self.h, out.ctypes.data))
+        return out
 
     def set_small_batch_ops(self, max_ops):
         """Largest batch (CIGAR ops) of the small-batch (two-launch) path; 0 forces the streaming path."""

@@ -140,6 +140,29 @@ int svx_stage_reserve(svx_ctx* ctx, size_t total) {
     return grow(ctx, &ctx->stage, &ctx->stage_bytes, total);
 }
 
+// Test facility (include/svx.h, "the scratch contract"): plain memsets and one copy, no kernel.
+extern "C" int svx_ctx_scratch_fill(svx_ctx* ctx, int byte) {
+    if (!ctx) return SVX_E_INVALID;
+    const int b = byte & 0xFF;
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->ws && ctx->ws_bytes > 4096) SVX_HIP(ctx, hipMemset(ctx->ws + 4096, b, ctx->ws_bytes - 4096));
+    if (ctx->stage && ctx->stage_bytes) SVX_HIP(ctx, hipMemset(ctx->stage, b, ctx->stage_bytes));
+    if (ctx->hpin && ctx->hpin_bytes) memset(ctx->hpin, b, ctx->hpin_bytes);
+    SVX_HIP(ctx, hipDeviceSynchronize());  // hipMemset may return before the device has finished it
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVX_OK;
+}
+
+extern "C" int svx_ctx_scratch_header(svx_ctx* ctx, uint32_t out[1024]) {
+    if (!ctx || !out) return SVX_E_INVALID;
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memset(out, 0, 4096);
+    if (ctx->ws) SVX_HIP(ctx, hipMemcpy(out, ctx->ws, 4096, hipMemcpyDeviceToHost));
+    return SVX_OK;
+}
+
 extern "C" int svx_ctx_set_small_batch_ops(svx_ctx* ctx, uint64_t max_ops) {
     if (!ctx) return SVX_E_INVALID;
     ctx->small_batch_ops = max_ops > (1ull << 23) ? (1ull << 23) : max_ops;  // the limit include/svx.h states

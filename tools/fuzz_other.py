@@ -3,7 +3,10 @@
 svx_segments_classify, svx_segments_postpass, svx_pair_partition, svx_edit_distance_batch,
 svx_haplotype_distance_batch, svx_linkage_cut_batch, svx_cigar_stats, svx_collect_batch (the pair sort on all three plans).
 
-    python tools/fuzz_other.py [--seconds 120] [--seed 1]
+    python tools/fuzz_other.py [--seconds 120] [--seed 1] [--poison]
+
+--poison: before every case the context's scratch (workspace, staging region, page-locked block) is filled with a
+byte drawn from the case's rng (svx_ctx_scratch_fill): what a call finds there between calls is unspecified.
 """
 import argparse
 import os
@@ -305,6 +308,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--only", default="", help="one of the fuzz_* functions, e.g. pair")
+    ap.add_argument("--poison", action="store_true", help="fill the context's scratch with a random byte before every case")
     a = ap.parse_args()
     ctx = _lib.default_context(0)
     fns = [fuzz_segments, fuzz_pair, fuzz_edit, fuzz_stats, fuzz_linkage, fuzz_postpass, fuzz_haplotypes, fuzz_collect, fuzz_inflate]
@@ -315,9 +319,13 @@ def main():
     while time.time() - t0 < a.seconds:
         f = fns[seed % len(fns)]
         rng = np.random.default_rng(seed)
+        fill = None
+        if a.poison:  # (the first draw of the case's rng: a seed names other inputs with the flag than without)
+            fill = int(rng.integers(0, 256))
+            ctx.scratch_fill(fill)
         ok, what = f(ctx, rng)
         if not ok:
-            print("MISMATCH seed %d: %s" % (seed, what))
+            print("MISMATCH seed %d%s: %s" % (seed, "" if fill is None else " --poison (fill 0x%02X)" % fill, what))
             sys.exit(1)
         counts[f.__name__] += 1
         seed += 1
