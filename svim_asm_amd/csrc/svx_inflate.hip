@@ -20,6 +20,14 @@
 // blocks; anything malformed (over-subscribed or incomplete code sets — except the one-code set zlib allows —, distances
 // beyond the output so far, output beyond ISIZE, input that ends early) ends the member with a status, never with an access
 // outside the member's input and output (and their documented padding: include/svx.h).
+// What is written once: the lane-per-member decoders (form 1, and k_inflate_parse of forms 2-3 — the judge of every
+// malformed stream) share the table block HuffLds, huff_construct / huff_table, the code walk (code_walk) and the block
+// header (block_header, a template over the two bit readers: k_inflate_parse calls it out of line, form 1 in line), so a
+// rule that decides a member's status stands in one place; so do length_code / distance_code (RFC 1951 §3.2.5).  The wave
+// parse keeps a header of its own (wave_header: all lanes together, and it judges nothing), and wave_decode its own text of
+// the §3.2.5 arithmetic: on the shared functions k_inflate_wparse kept its registers (128 VGPRs, no scratch) but the
+// shipped form took 3.05 -> 3.11 ms for 1 000 members and 6.91 -> 7.02 for 7 261, outside the parent's spreads of 0.03 and
+// 0.09 (profiles/inflate_one_parser_ab.txt).
 // Integer / byte work, no MFMA.  Form 3 is bound by instruction issue (~70 VALU per symbol and pass, two passes and a write
 // pass per window), forms 1-2 by a member's serial chain.
 #include <atomic>
@@ -39,7 +47,7 @@ constexpr int kLanes = SVX_INFL_LANES;  // members per workgroup (their LDS tabl
 #endif
 // Lanes of a wave that hold a member.  The lanes of a wave are at different points of their streams, and every distinct
 // path is issued for the whole wave: the fewer members share a wave, the shorter each one's decode — and the more waves
-// the same number of members in flight needs (110 VGPRs: 16 waves per CU).  7 261 SEQ members, kernel time
+// the same number of members in flight needs (four waves a SIMD by its registers: 16 per CU).  7 261 SEQ members, kernel time
 // (profiles/r05_inflate_geometry.txt): 32 per wave 58 ms (16 k members in flight on the chip), 4 per wave 49 (16 k),
 // 2 per wave 34.5 (8 k), 1 per wave 23 ms up to the 4 096 it holds at once, 48 beyond.  Four per wave keeps the chip's
 // capacity of 64 members per CU (4 workgroups of 16 members: 39 KB of LDS each) — a sample's two readers bring 13-14 k.
@@ -61,8 +69,11 @@ struct InfArgs {
     uint32_t n;
 };
 
-struct Lds {
-    uint32_t crc_table4[4][256];  // slicing-by-4 tables of CRC-32 (reflected 0xEDB88320)
+// ==================================================================================================================
+// What the two lane-per-member forms share: the Huffman tables of a member's block in LDS, the code walk, the RFC 1951
+// §3.2.5 arithmetic and ONE block-header parser (block_header), a template over the form's bit reader.
+// The tables of sixteen members, [..][member]: the lanes of a wave reading the same index hit different banks.
+struct HuffLds {
     uint16_t tab_ll[1 << kLLBits][kLanes];  // next kLLBits bits -> symbol << 4 | code length (0: a longer code)
     uint16_t tab_d[1 << kDBits][kLanes];
     uint16_t cnt_ll[kMaxBits + 1][kLanes];
@@ -72,24 +83,108 @@ struct Lds {
     uint8_t lens4[(kLL + kDist + 2) / 2][kLanes];  // code lengths of the block being set up, two per byte
 };
 
-__device__ __forceinline__ uint32_t len_get(const Lds& s, int i, int lane) { return (s.lens4[i >> 1][lane] >> (4 * (i & 1))) & 15u; }
-__device__ __forceinline__ void len_set(Lds& s, int i, int lane, uint32_t v) {
+__device__ __forceinline__ uint32_t len_get(const HuffLds& t, int i, int lane) { return (t.lens4[i >> 1][lane] >> (4 * (i & 1))) & 15u; }
+__device__ __forceinline__ void len_set(HuffLds& t, int i, int lane, uint32_t v) {
     const uint32_t sh = 4 * (i & 1);
-    s.lens4[i >> 1][lane] = (uint8_t)((s.lens4[i >> 1][lane] & ~(15u << sh)) | ((v & 15u) << sh));
+    t.lens4[i >> 1][lane] = (uint8_t)((t.lens4[i >> 1][lane] & ~(15u << sh)) | ((v & 15u) << sh));
 }
+
+// The per-length code counts of the block's two codes, in registers (two 16-bit counts per word) for the whole block:
+// the code walk below is then pure arithmetic plus ONE LDS read for the symbol.
+struct Counts {
+    uint32_t w[8];  // w[k] = count[2k] | count[2k + 1] << 16
+};
+__device__ __forceinline__ Counts load_counts(const uint16_t (*cnt)[kLanes], int lane) {  // cnt[0..15][lane]
+    Counts c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c.w[k] = (uint32_t)cnt[2 * k][lane] | ((uint32_t)cnt[2 * k + 1][lane] << 16);
+    return c;
+}
+
+// puff.c's decode() on the register-resident counts, one bit per step: the code-length code of a dynamic block's header,
+// and the codes the look-up tables do not hold (longer than 9 / 7 bits).  `sym`: the sorted symbols, [index][member].
+// Returns symbol << 8 | bits used, or -1.
+__device__ __forceinline__ int code_walk(uint32_t bitbuf, const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    int code = 0, first = 0, index = 0;
+#pragma unroll
+    for (int len = 1; len <= kMaxBits; ++len) {
+        code |= (int)(bitbuf & 1u);
+        bitbuf >>= 1;
+        const int count = (int)((c.w[len >> 1] >> (16 * (len & 1))) & 0xFFFFu);
+        if (code - count < first) return ((int)sym[index + (code - first)][lane] << 8) | len;
+        index += count;
+        first += count;
+        first <<= 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+// The look-up table of a code set that huff_construct has laid out (counts + symbols sorted by code): the canonical
+// code of the k-th symbol of length l is first(l) + k; its bits arrive LSB first, so the table index is the code
+// bit-reversed, repeated for every value of the index bits behind it.
+template <int BITS>
+__device__ __forceinline__ void huff_table(uint16_t (*tab)[kLanes], const uint16_t (*cnt)[kLanes], const uint16_t (*sym)[kLanes], int lane) {
+    for (int i = 0; i < (1 << BITS); ++i) tab[i][lane] = 0;
+    uint32_t code = 0, index = 0;
+    for (int l = 1; l <= BITS; ++l) {
+        const uint32_t n = cnt[l][lane];
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t rev = __brev(code + k) >> (32 - l);
+            const uint16_t e = (uint16_t)(((uint32_t)sym[index + k][lane] << 4) | (uint32_t)l);
+            for (uint32_t i = rev; i < (1u << BITS); i += 1u << l) tab[i][lane] = e;
+        }
+        code = (code + n) << 1;
+        index += n;
+    }
+}
+
+// puff.c's construct() over the code lengths [base, base + n): counts per length, symbols sorted by (length, symbol).
+// Returns 0 complete, > 0 incomplete, < 0 over-subscribed.
+__device__ __forceinline__ int huff_construct(uint16_t (*cnt)[kLanes], uint16_t (*sym)[kLanes], const HuffLds& t, int base, int n, int lane) {
+    for (int l = 0; l <= kMaxBits; ++l) cnt[l][lane] = 0;
+    for (int s = 0; s < n; ++s) cnt[len_get(t, base + s, lane)][lane] += 1;
+    if (cnt[0][lane] == n) return 0;  // no codes: complete, but decoding will fail
+    int left = 1;
+    for (int l = 1; l <= kMaxBits; ++l) {
+        left <<= 1;
+        left -= cnt[l][lane];
+        if (left < 0) return left;
+    }
+    uint16_t offs[kMaxBits + 1];
+    offs[1] = 0;
+    for (int l = 1; l < kMaxBits; ++l) offs[l + 1] = offs[l] + cnt[l][lane];
+    for (int s = 0; s < n; ++s) {
+        const int l = (int)len_get(t, base + s, lane);
+        if (l) sym[offs[l]++][lane] = (uint16_t)s;
+    }
+    return left;
+}
+
+// Length and distance bases / extra-bit counts by arithmetic (RFC 1951 §3.2.5: four codes per power of two for lengths,
+// two for distances) instead of table look-ups in memory.
+struct BaseExtra {
+    uint32_t base, extra;
+};
+__device__ __forceinline__ BaseExtra length_code(uint32_t li) {  // li = symbol - 257: 0..28
+    if (li < 8u) return {3u + li, 0u};
+    if (li == 28u) return {258u, 0u};
+    const uint32_t e = (li - 4u) >> 2;
+    return {3u + ((4u + (li & 3u)) << e), e};
+}
+__device__ __forceinline__ BaseExtra distance_code(uint32_t ds) {  // 0..29
+    if (ds < 4u) return {1u + ds, 0u};
+    const uint32_t ex = (ds - 2u) >> 1;
+    return {1u + ((2u + (ds & 1u)) << ex), ex};
+}
+
+__device__ const uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+enum { ST_OK = 0, ST_BAD_STREAM = 1, ST_SIZE = 2, ST_CRC = 3, ST_INPUT_END = 4 };
 
 typedef uint32_t u32_unaligned __attribute__((aligned(1)));
 typedef uint64_t u64_unaligned __attribute__((aligned(1)));
 typedef uint16_t u16_unaligned __attribute__((aligned(1)));
-
-struct Bits {
-    const uint8_t* p;
-    uint32_t len, pos;   // pos: bytes consumed into buf/next so far
-    uint64_t buf;
-    uint32_t cnt;
-    uint32_t next;       // the word after the ones in buf, requested ahead
-    uint32_t next_bytes; // how many real bytes `next` holds (0..4)
-};
 
 // The input word at byte position pos, zero-padded behind the member's end — WITHOUT a branch: the refill requests
 // it several symbols before it is used, and a load that sits behind control flow is waited for at once (a wait is
@@ -105,13 +200,28 @@ __device__ __forceinline__ uint32_t load_word(const uint8_t* p, uint32_t pos, ui
     return skip >= 4 ? 0u : w >> (8 * skip);
 }
 
+// ---- The two bit readers.  Both keep `buf` (the next `cnt` bits), `pos` (input bytes taken into buf / next so far) and
+// the word behind buf, `next`; they differ in where `next` comes from, which is refill(b, s, lane) alone — everything else
+// of a reader is the templates behind them, and the code that reads bits names its reader as (b, s, lane).
+// Form 1: the member's input in global memory, the word behind `next` requested ahead.
+struct Lds {
+    uint32_t crc_table4[4][256];  // slicing-by-4 tables of CRC-32 (reflected 0xEDB88320)
+    HuffLds huff;
+};
+struct Bits {
+    const uint8_t* p;
+    uint32_t len, pos;
+    uint64_t buf;
+    uint32_t cnt;
+    uint32_t next;
+    uint32_t next_bytes; // how many real bytes `next` holds (0..4)
+};
 __device__ __forceinline__ void bits_init(Bits& b, const uint8_t* p, uint32_t len) {
     b.p = p; b.len = len; b.pos = 0; b.buf = 0; b.cnt = 0;
     b.next = load_word(p, 0, len, &b.next_bytes);
 }
-
-// at least 32 valid (or zero-padded) bits afterwards; `over` counts padding bits handed out beyond the input
-__device__ __forceinline__ void bits_refill(Bits& b) {
+// at least 32 valid (or zero-padded) bits afterwards
+__device__ __forceinline__ void refill(Bits& b, const Lds&, int) {
     if (b.cnt <= 32) {
         b.buf |= (uint64_t)b.next << b.cnt;
         b.cnt += 32;
@@ -120,132 +230,210 @@ __device__ __forceinline__ void bits_refill(Bits& b) {
     }
 }
 
-__device__ __forceinline__ uint32_t bits_get(Bits& b, uint32_t n) {  // n <= 16
-    bits_refill(b);
-    const uint32_t v = (uint32_t)b.buf & ((1u << n) - 1u);
+// Forms 2 and 3 (k_inflate_parse): the member's input travels through a 128-byte LDS ring; the ring holds the input bytes
+// [.., ring_hi), zero behind the member's end.
+constexpr int kRingBytes = 128;  // per member: 2 refills of 64 bytes
+struct ParseLds {
+    HuffLds huff;
+    uint32_t ring[kRingBytes / 4][kLanes];   // [word][member]: lanes reading the same word index hit different banks
+    uint32_t in_lo[kLanes], in_hi[kLanes], in_len[kLanes], ring_hi[kLanes], rd_pos[kLanes];  // what the refill lanes need of a member
+};
+// (the LDS layout both kernels were measured with: the tables behind the CRC tables, and in front of the ring)
+static_assert(sizeof(Lds) == 4096 + sizeof(HuffLds) && offsetof(ParseLds, huff) == 0 && offsetof(ParseLds, ring) == sizeof(HuffLds),
+              "HuffLds sits behind crc_table4 in Lds and first in ParseLds");
+struct RBits {
+    uint64_t buf;
+    uint32_t cnt, pos, next, ring_hi, in_len;
+    const uint8_t* in;
+};
+// 64 more bytes into THIS lane's ring by the lane itself (block headers take their bits in long runs; the symbol loop
+// is topped up by the whole wave, k_inflate_parse)
+// (out of line, like the walk below and the block header: the symbol loop has to stay small enough for the instruction
+//  cache — inlined at every refill site the kernel was 150 KB of code and a step took 1 300 clocks)
+// (arguments by value: a reference would pin the caller's bit reader to scratch memory)
+__device__ __noinline__ void rb_fill_words(const uint8_t* in, uint32_t ring_hi, uint32_t in_len, ParseLds& s, int lane) {
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { uint32_t real; w[k] = load_word(in, ring_hi + 4u * k, in_len, &real); }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s.ring[((ring_hi >> 2) + k) & (kRingBytes / 4 - 1)][lane] = w[k];
+}
+__device__ __forceinline__ void rb_fill_self(RBits& b, ParseLds& s, int lane) {
+    rb_fill_words(b.in, b.ring_hi, b.in_len, s, lane);
+    b.ring_hi += 64;
+}
+__device__ __forceinline__ void refill(RBits& b, ParseLds& s, int lane) {
+    if (b.cnt <= 32) {
+        b.buf |= (uint64_t)b.next << b.cnt;
+        b.cnt += 32;
+        b.pos += 4;
+        if (b.pos + 4 > b.ring_hi) rb_fill_self(b, s, lane);
+        b.next = s.ring[(b.pos >> 2) & (kRingBytes / 4 - 1)][lane];
+    }
+}
+
+// The code at the head of a reader's bits (32 of them are there), by the walk.  Form 1 walks in place; k_inflate_parse
+// calls out of line: its symbol loop must stay small for the instruction cache (see rb_fill_words).
+__device__ __noinline__ int rb_walk_cold(uint32_t bitbuf, const Counts c, const uint16_t (*sym)[kLanes], int lane) {
+    return code_walk(bitbuf, c, sym, lane);
+}
+__device__ __forceinline__ int code_at_head(const Bits& b, const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    return code_walk((uint32_t)b.buf, c, sym, lane);
+}
+__device__ __forceinline__ int code_at_head(const RBits& b, const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    return rb_walk_cold((uint32_t)b.buf, c, sym, lane);
+}
+
+// ---- a reader's surface: B is Bits or RBits, S the kernel's LDS block
+template <typename B>
+__device__ __forceinline__ void drop_bits(B& b, uint32_t n) {
     b.buf >>= n;
     b.cnt -= n;
+}
+template <typename B>
+__device__ __forceinline__ void drop_to_byte(B& b) { drop_bits(b, b.cnt & 7u); }
+template <typename B, typename S>
+__device__ __forceinline__ uint32_t get_bits(B& b, S& s, int lane, uint32_t n) {  // n <= 16
+    refill(b, s, lane);
+    const uint32_t v = (uint32_t)b.buf & ((1u << n) - 1u);
+    drop_bits(b, n);
     return v;
 }
-
-// bits consumed so far; more than 8 * len means the stream ran past its input
-__device__ __forceinline__ uint64_t bits_used(const Bits& b) { return (uint64_t)b.pos * 8 - b.cnt; }
-
-// The per-length code counts of the block's two codes, in registers (two 16-bit counts per word) for the whole block:
-// the decode walk below is then pure arithmetic plus ONE LDS read for the symbol.
-struct Counts {
-    uint32_t w[8];  // w[k] = count[2k] | count[2k + 1] << 16
-};
-template <typename CNT>
-__device__ __forceinline__ Counts load_counts(CNT cnt, int lane) {  // cnt[0..15][lane]
-    Counts c;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c.w[k] = (uint32_t)cnt[2 * k][lane] | ((uint32_t)cnt[2 * k + 1][lane] << 16);
-    return c;
+// bits consumed so far; more than 8 * the input's length means the stream ran past its input (the readers hand out zeros there)
+template <typename B>
+__device__ __forceinline__ uint64_t bits_used(const B& b) { return (uint64_t)b.pos * 8 - b.cnt; }
+// The extra bits of a distance code, up to 13: two reads keep each within the refill guarantee.  (The first read takes up
+// to 8 of them; written as `n > 8 ? two reads : one`, k_inflate_parse compiled to 102 VGPRs, not 98, and forms 1 and 2
+// took 1-2 ms more.)
+template <typename B, typename S>
+__device__ __forceinline__ uint32_t get_extra(B& b, S& s, int lane, uint32_t n) {
+    uint32_t v = get_bits(b, s, lane, n > 8 ? 8u : n);
+    if (n > 8) v |= get_bits(b, s, lane, n - 8) << 8;
+    return v;
 }
-
-// puff.c's decode() alone (the code-length code of a dynamic block: 19 symbols, used a few hundred times)
-template <typename SYM>
-__device__ __forceinline__ int huff_walk(Bits& b, const Counts& c, SYM sym, int lane) {
-    bits_refill(b);
-    uint32_t bitbuf = (uint32_t)b.buf;
-    int code = 0, first = 0, index = 0;
-#pragma unroll
-    for (int len = 1; len <= kMaxBits; ++len) {
-        code |= (int)(bitbuf & 1u);
-        bitbuf >>= 1;
-        const int count = (int)((c.w[len >> 1] >> (16 * (len & 1))) & 0xFFFFu);
-        if (code - count < first) {
-            b.buf >>= len;
-            b.cnt -= len;
-            return sym[index + (code - first)][lane];
-        }
-        index += count;
-        first += count;
-        first <<= 1;
-        code <<= 1;
-    }
-    return -1;
+// the symbol at the head of the bits (32 of them are there) by the walk, or -1
+template <typename B>
+__device__ __forceinline__ int walk_symbol(B& b, const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    const int r = code_at_head(b, c, sym, lane);
+    if (r < 0) return -1;
+    drop_bits(b, (uint32_t)r & 255u);
+    return r >> 8;
 }
-
+// One symbol by the walk alone (the code-length code of a dynamic block: 19 symbols, used a few hundred times), or -1
+template <typename B, typename S>
+__device__ __forceinline__ int huff_walk(B& b, S& s, const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    refill(b, s, lane);
+    return walk_symbol(b, c, sym, lane);
+}
 // One symbol: the next BITS bits index the block's table (entry = symbol << 4 | length); codes longer than BITS bits
-// (entry 0) take puff.c's walk over the code lengths, one bit per step, on the register-resident counts.
-template <int BITS, typename TAB, typename SYM>
-__device__ __forceinline__ int huff_decode(Bits& b, TAB tab, const Counts& c, SYM sym, int lane) {
-    bits_refill(b);
-    uint32_t bitbuf = (uint32_t)b.buf;
-    const uint32_t e = tab[bitbuf & ((1u << BITS) - 1u)][lane];
-    if (e) {
-        const uint32_t len = e & 15u;
-        b.buf >>= len;
-        b.cnt -= len;
+// (entry 0) take the walk over the code lengths.
+template <int BITS, typename B, typename S>
+__device__ __forceinline__ int huff_decode(B& b, S& s, const uint16_t (*tab)[kLanes], const Counts& c, const uint16_t (*sym)[kLanes], int lane) {
+    refill(b, s, lane);
+    const uint32_t e = tab[(uint32_t)b.buf & ((1u << BITS) - 1u)][lane];
+    if (__builtin_expect(e != 0u, 1)) {
+        drop_bits(b, e & 15u);
         return (int)(e >> 4);
     }
-    int code = 0, first = 0, index = 0;
-#pragma unroll
-    for (int len = 1; len <= kMaxBits; ++len) {
-        code |= (int)(bitbuf & 1u);
-        bitbuf >>= 1;
-        const int count = (int)((c.w[len >> 1] >> (16 * (len & 1))) & 0xFFFFu);
-        if (code - count < first) {
-            b.buf >>= len;
-            b.cnt -= len;
-            return sym[index + (code - first)][lane];
+    return walk_symbol(b, c, sym, lane);
+}
+
+enum { PS_HEADER = 0, PS_SYM = 1, PS_STORED = 2, PS_DONE = 3 };
+
+// what a member's lane carries through its stream
+template <typename B>
+struct LaneState {
+    B b;
+    Counts c_ll, c_d;
+    uint32_t isize, produced, st, stored_left;
+    bool last;
+};
+
+// A block header: type, (for dynamic codes) the code lengths, the tables of the block.  Returns the lane's next state:
+// PS_SYM with the tables and h.c_ll / h.c_d; PS_STORED with h.stored_left bytes for the caller to copy; PS_DONE with
+// h.st.  THE judge of a malformed header for forms 1 and 2, and through k_inflate_parse for form 3.
+template <typename B, typename S>
+__device__ __forceinline__ int block_header(LaneState<B>& h, S& s, const int lane) {
+    B& b = h.b;
+    HuffLds& t = s.huff;
+    h.last = get_bits(b, s, lane, 1) != 0;
+    const uint32_t type = get_bits(b, s, lane, 2);
+    if (type == 0) {  // stored: skip to the byte boundary, LEN / NLEN, raw bytes
+        drop_to_byte(b);
+        const uint32_t len = get_bits(b, s, lane, 16), nlen = get_bits(b, s, lane, 16);
+        if ((len ^ 0xFFFFu) != nlen) { h.st = ST_BAD_STREAM; return PS_DONE; }
+        if (h.produced + len > h.isize) { h.st = ST_SIZE; return PS_DONE; }
+        h.stored_left = len;
+        return PS_STORED;
+    }
+    if (type == 3) { h.st = ST_BAD_STREAM; return PS_DONE; }
+    bool good = true;
+    if (type == 1) {  // fixed codes
+        for (int i = 0; i < 144; ++i) len_set(t, i, lane, 8);
+        for (int i = 144; i < 256; ++i) len_set(t, i, lane, 9);
+        for (int i = 256; i < 280; ++i) len_set(t, i, lane, 7);
+        for (int i = 280; i < kLL; ++i) len_set(t, i, lane, 8);
+        for (int i = 0; i < kDist; ++i) len_set(t, kLL + i, lane, 5);
+        huff_construct(t.cnt_ll, t.sym_ll, t, 0, kLL, lane);
+        huff_construct(t.cnt_d, t.sym_d, t, kLL, kDist, lane);
+    } else {  // dynamic codes
+        const uint32_t nlen = get_bits(b, s, lane, 5) + 257, ndist = get_bits(b, s, lane, 5) + 1, ncode = get_bits(b, s, lane, 4) + 4;
+        good = nlen <= 286 && ndist <= 30;
+        if (good) {
+            for (int i = 0; i < 19; ++i) len_set(t, i, lane, 0);
+            for (uint32_t i = 0; i < ncode; ++i) len_set(t, kClOrder[i], lane, get_bits(b, s, lane, 3));
+            // the code-length code borrows the distance tables (19 symbols); its own lengths are not needed any more once
+            // it is built, so the literal/length + distance lengths it encodes are decoded into the same array from 0
+            good = huff_construct(t.cnt_d, t.sym_d, t, 0, 19, lane) == 0;  // (zlib: must be complete)
         }
-        index += count;
-        first += count;
-        first <<= 1;
-        code <<= 1;
-    }
-    return -1;
-}
-
-// The look-up table of a code set that huff_construct has laid out (counts + symbols sorted by code): the canonical
-// code of the k-th symbol of length l is first(l) + k; its bits arrive LSB first, so the table index is the code
-// bit-reversed, repeated for every value of the index bits behind it.
-template <int BITS, typename TAB, typename CNT, typename SYM>
-__device__ __forceinline__ void huff_table(TAB tab, CNT cnt, SYM sym, int lane) {
-    for (int i = 0; i < (1 << BITS); ++i) tab[i][lane] = 0;
-    uint32_t code = 0, index = 0;
-    for (int l = 1; l <= BITS; ++l) {
-        const uint32_t n = cnt[l][lane];
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t rev = __brev(code + k) >> (32 - l);
-            const uint16_t e = (uint16_t)(((uint32_t)sym[index + k][lane] << 4) | (uint32_t)l);
-            for (uint32_t i = rev; i < (1u << BITS); i += 1u << l) tab[i][lane] = e;
+        if (good) {
+            const Counts cl_counts = load_counts(t.cnt_d, lane);
+            uint32_t idx = 0;
+            while (good && idx < nlen + ndist) {
+                const int sym = huff_walk(b, s, cl_counts, t.sym_d, lane);
+                if (sym < 0) { good = false; }
+                else if (sym < 16) { len_set(t, (int)idx++, lane, (uint32_t)sym); }
+                else {
+                    uint32_t prev = 0, rep = 0;
+                    if (sym == 16) {
+                        if (idx == 0) good = false;
+                        else { prev = len_get(t, (int)idx - 1, lane); rep = 3 + get_bits(b, s, lane, 2); }
+                    } else if (sym == 17) {
+                        rep = 3 + get_bits(b, s, lane, 3);
+                    } else {
+                        rep = 11 + get_bits(b, s, lane, 7);
+                    }
+                    if (good && idx + rep > nlen + ndist) good = false;
+                    while (good && rep--) len_set(t, (int)idx++, lane, prev);
+                }
+            }
         }
-        code = (code + n) << 1;
-        index += n;
+        if (good) good = len_get(t, 256, lane) != 0;  // no end-of-block code
+        if (good) {
+            // the distance lengths follow the literal/length ones: move them to their own region (from the back: the
+            // regions may overlap and the destination lies behind the source), pad both with zeros
+            for (int i = (int)ndist - 1; i >= 0; --i) len_set(t, kLL + i, lane, len_get(t, (int)nlen + i, lane));
+            for (uint32_t i = nlen; i < (uint32_t)kLL; ++i) len_set(t, (int)i, lane, 0);
+            for (uint32_t i = ndist; i < (uint32_t)kDist; ++i) len_set(t, kLL + (int)i, lane, 0);
+            // incomplete code sets are allowed only when they consist of ONE code of length 1 (zlib inflate_table)
+            int err = huff_construct(t.cnt_ll, t.sym_ll, t, 0, kLL, lane);
+            if (err < 0 || (err > 0 && kLL != (int)t.cnt_ll[0][lane] + (int)t.cnt_ll[1][lane])) good = false;
+            if (good) {
+                err = huff_construct(t.cnt_d, t.sym_d, t, kLL, kDist, lane);
+                if (err < 0 || (err > 0 && kDist != (int)t.cnt_d[0][lane] + (int)t.cnt_d[1][lane])) good = false;
+            }
+        }
     }
+    if (!good) { h.st = ST_BAD_STREAM; return PS_DONE; }
+    huff_table<kLLBits>(t.tab_ll, t.cnt_ll, t.sym_ll, lane);
+    huff_table<kDBits>(t.tab_d, t.cnt_d, t.sym_d, lane);
+    h.c_ll = load_counts(t.cnt_ll, lane);
+    h.c_d = load_counts(t.cnt_d, lane);
+    return PS_SYM;
 }
 
-// puff.c's construct(): counts per length, symbols sorted by (length, symbol).  Returns 0 complete, > 0 incomplete,
-// < 0 over-subscribed.
-template <typename CNT, typename SYM>
-__device__ __forceinline__ int huff_construct(CNT cnt, SYM sym, const Lds& lds, int base, int n, int lane) {
-    for (int l = 0; l <= kMaxBits; ++l) cnt[l][lane] = 0;
-    for (int s = 0; s < n; ++s) cnt[len_get(lds, base + s, lane)][lane] += 1;
-    if (cnt[0][lane] == n) return 0;  // no codes: complete, but decoding will fail
-    int left = 1;
-    for (int l = 1; l <= kMaxBits; ++l) {
-        left <<= 1;
-        left -= cnt[l][lane];
-        if (left < 0) return left;
-    }
-    uint16_t offs[kMaxBits + 1];
-    offs[1] = 0;
-    for (int l = 1; l < kMaxBits; ++l) offs[l + 1] = offs[l] + cnt[l][lane];
-    for (int s = 0; s < n; ++s) {
-        const int l = (int)len_get(lds, base + s, lane);
-        if (l) sym[offs[l]++][lane] = (uint16_t)s;
-    }
-    return left;
-}
-
-__device__ const uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-enum { ST_OK = 0, ST_BAD_STREAM = 1, ST_SIZE = 2, ST_CRC = 3, ST_INPUT_END = 4 };
-
+// ==================================================================================================================
+// Form 1: one launch, a lane per member that decodes, copies its matches from its own earlier output and takes the CRC.
 #ifdef SVX_INFL_WAVES  // waves per SIMD the register allocator must leave room for (experiments: tools/r05_infl_geom.sh)
 #define SVX_INFL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(SVX_INFL_WAVES, SVX_INFL_WAVES)))
 #else
@@ -254,6 +442,7 @@ enum { ST_OK = 0, ST_BAD_STREAM = 1, ST_SIZE = 2, ST_CRC = 3, ST_INPUT_END = 4 }
 __global__ __launch_bounds__(kThreads) SVX_INFL_OCCUPANCY void k_bgzf_inflate(InfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     Lds& s = *reinterpret_cast<Lds*>(lds_raw);
+    const HuffLds& ht = s.huff;
     const int lane = (int)(threadIdx.x >> 6) * kActive + (int)(threadIdx.x & 63u);  // this thread's member slot, if it has one
     const bool holds_member = (threadIdx.x & 63u) < (uint32_t)kActive;
     // CRC-32 (IEEE 802.3, reflected 0xEDB88320) table
@@ -273,151 +462,61 @@ __global__ __launch_bounds__(kThreads) SVX_INFL_OCCUPANCY void k_bgzf_inflate(In
     __syncthreads();
     const uint32_t m = blockIdx.x * kLanes + lane;
     if (!holds_member || m >= a.n) return;
-    const uint8_t* in = a.in + a.in_off[m];
     const uint32_t in_len = a.in_len[m], isize = a.isize[m];
     uint8_t* out = a.out + a.out_off[m];
-    Bits b;
-    bits_init(b, in, in_len);
-    uint32_t produced = 0, st = ST_OK;
+    LaneState<Bits> h;
+    Bits& b = h.b;
+    bits_init(b, a.in + a.in_off[m], in_len);
+    h.isize = isize; h.produced = 0; h.st = ST_OK; h.stored_left = 0; h.last = false;
     if (isize > 65536u) {  // no BGZF member is longer: a wrong trailer must not move the output limit
         a.status[m] = ST_SIZE;
         return;
     }
-    bool last = false;
-    while (!last && st == ST_OK) {
-        last = bits_get(b, 1) != 0;
-        const uint32_t type = bits_get(b, 2);
-        if (type == 0) {  // stored: skip to the byte boundary, LEN / NLEN, raw bytes
-            const uint32_t drop = b.cnt & 7u;
-            b.buf >>= drop;
-            b.cnt -= drop;
-            const uint32_t len = bits_get(b, 16), nlen = bits_get(b, 16);
-            if ((len ^ 0xFFFFu) != nlen) { st = ST_BAD_STREAM; break; }
-            if (produced + len > isize) { st = ST_SIZE; break; }
-            for (uint32_t i = 0; i < len; ++i) out[produced++] = (uint8_t)bits_get(b, 8);
-            if (bits_used(b) > (uint64_t)in_len * 8) st = ST_INPUT_END;
-            continue;
-        }
-        if (type == 3) { st = ST_BAD_STREAM; break; }
-        if (type == 1) {  // fixed codes
-            for (int i = 0; i < 144; ++i) len_set(s, i, lane, 8);
-            for (int i = 144; i < 256; ++i) len_set(s, i, lane, 9);
-            for (int i = 256; i < 280; ++i) len_set(s, i, lane, 7);
-            for (int i = 280; i < kLL; ++i) len_set(s, i, lane, 8);
-            for (int i = 0; i < kDist; ++i) len_set(s, kLL + i, lane, 5);
-            huff_construct(s.cnt_ll, s.sym_ll, s, 0, kLL, lane);
-            huff_construct(s.cnt_d, s.sym_d, s, kLL, kDist, lane);
-        } else {  // dynamic codes
-            const uint32_t nlen = bits_get(b, 5) + 257, ndist = bits_get(b, 5) + 1, ncode = bits_get(b, 4) + 4;
-            if (nlen > 286 || ndist > 30) { st = ST_BAD_STREAM; break; }
-            for (int i = 0; i < 19; ++i) len_set(s, i, lane, 0);
-            for (uint32_t i = 0; i < ncode; ++i) len_set(s, kClOrder[i], lane, bits_get(b, 3));
-            // the code-length code borrows the distance tables (19 symbols); its own lengths are not needed any more once
-            // it is built, so the literal/length + distance lengths it encodes are decoded into the same array from 0
-            if (huff_construct(s.cnt_d, s.sym_d, s, 0, 19, lane) != 0) { st = ST_BAD_STREAM; break; }  // (zlib: must be complete)
-            const Counts cl_counts = load_counts(s.cnt_d, lane);
-            uint32_t idx = 0;
-            while (idx < nlen + ndist && st == ST_OK) {
-                const int sym = huff_walk(b, cl_counts, s.sym_d, lane);
-                if (sym < 0) { st = ST_BAD_STREAM; break; }
-                if (sym < 16) {
-                    len_set(s, (int)idx++, lane, (uint32_t)sym);
-                } else {
-                    uint32_t prev = 0, rep;
-                    if (sym == 16) {
-                        if (idx == 0) { st = ST_BAD_STREAM; break; }
-                        prev = len_get(s, (int)idx - 1, lane);
-                        rep = 3 + bits_get(b, 2);
-                    } else if (sym == 17) {
-                        rep = 3 + bits_get(b, 3);
-                    } else {
-                        rep = 11 + bits_get(b, 7);
-                    }
-                    if (idx + rep > nlen + ndist) { st = ST_BAD_STREAM; break; }
-                    while (rep--) len_set(s, (int)idx++, lane, prev);
+    do {
+        const int next = block_header(h, s, lane);
+        if (next == PS_DONE) break;
+        if (next == PS_STORED) {
+            for (; h.stored_left; --h.stored_left) out[h.produced++] = (uint8_t)get_bits(b, s, lane, 8);
+        } else {  // ---- the block's symbols
+            for (;;) {
+                const int sym = huff_decode<kLLBits>(b, s, ht.tab_ll, h.c_ll, ht.sym_ll, lane);
+                if (sym < 0) { h.st = ST_BAD_STREAM; break; }
+                if (sym < 256) {
+                    if (h.produced >= isize) { h.st = ST_SIZE; break; }
+                    out[h.produced++] = (uint8_t)sym;
+                    continue;
                 }
-            }
-            if (st != ST_OK) break;
-            if (len_get(s, 256, lane) == 0) { st = ST_BAD_STREAM; break; }  // no end-of-block code
-            // the distance lengths follow the literal/length ones: move them to their own region (from the back: the
-            // regions may overlap and the destination lies behind the source), pad both with zeros
-            for (int i = (int)ndist - 1; i >= 0; --i) len_set(s, kLL + i, lane, len_get(s, (int)nlen + i, lane));
-            for (uint32_t i = nlen; i < (uint32_t)kLL; ++i) len_set(s, (int)i, lane, 0);
-            for (uint32_t i = ndist; i < (uint32_t)kDist; ++i) len_set(s, kLL + (int)i, lane, 0);
-            // incomplete code sets are allowed only when they consist of ONE code of length 1 (zlib inflate_table)
-            int err = huff_construct(s.cnt_ll, s.sym_ll, s, 0, kLL, lane);
-            if (err < 0 || (err > 0 && kLL != (int)s.cnt_ll[0][lane] + (int)s.cnt_ll[1][lane])) { st = ST_BAD_STREAM; break; }
-            err = huff_construct(s.cnt_d, s.sym_d, s, kLL, kDist, lane);
-            if (err < 0 || (err > 0 && kDist != (int)s.cnt_d[0][lane] + (int)s.cnt_d[1][lane])) { st = ST_BAD_STREAM; break; }
-        }
-        // ---- the block's symbols
-        huff_table<kLLBits>(s.tab_ll, s.cnt_ll, s.sym_ll, lane);
-        huff_table<kDBits>(s.tab_d, s.cnt_d, s.sym_d, lane);
-        const Counts c_ll = load_counts(s.cnt_ll, lane), c_d = load_counts(s.cnt_d, lane);
-        for (;;) {
-            const int sym = huff_decode<kLLBits>(b, s.tab_ll, c_ll, s.sym_ll, lane);
-            if (sym < 0) { st = ST_BAD_STREAM; break; }
-            if (sym < 256) {
-                if (produced >= isize) { st = ST_SIZE; break; }
-#ifdef SVX_EXP_INFL_NOLIT  // ablation: what the literal stores cost
-                ++produced;
-#else
-                out[produced++] = (uint8_t)sym;
-#endif
-                continue;
-            }
-            if (sym == 256) break;
-            const int li = sym - 257;
-            if (li >= 29) { st = ST_BAD_STREAM; break; }
-            // length and distance bases / extra-bit counts by arithmetic (RFC 1951 §3.2.5: four codes per power of two
-            // for lengths, two for distances) instead of table look-ups in memory
-            uint32_t len;
-            if (li < 8) {
-                len = 3u + (uint32_t)li;
-            } else if (li == 28) {
-                len = 258u;
-            } else {
-                const uint32_t e = ((uint32_t)li - 4u) >> 2;
-                len = 3u + ((4u + ((uint32_t)li & 3u)) << e) + bits_get(b, e);
-            }
-            const int ds = huff_decode<kDBits>(b, s.tab_d, c_d, s.sym_d, lane);
-            if (ds < 0 || ds >= 30) { st = ST_BAD_STREAM; break; }
-            uint32_t dist;
-            if (ds < 4) {
-                dist = 1u + (uint32_t)ds;
-            } else {
-                const uint32_t ex = ((uint32_t)ds - 2u) >> 1;
-                dist = 1u + ((2u + ((uint32_t)ds & 1u)) << ex);
-                if (ex > 8) {  // up to 13 extra bits: two reads keep each within the refill guarantee
-                    const uint32_t lo = bits_get(b, 8);
-                    dist += lo | (bits_get(b, ex - 8) << 8);
+                if (sym == 256) break;
+                const int li = sym - 257;
+                if (li >= 29) { h.st = ST_BAD_STREAM; break; }
+                const BaseExtra lc = length_code((uint32_t)li);
+                uint32_t len = lc.base;
+                if (lc.extra) len += get_bits(b, s, lane, lc.extra);
+                const int ds = huff_decode<kDBits>(b, s, ht.tab_d, h.c_d, ht.sym_d, lane);
+                if (ds < 0 || ds >= 30) { h.st = ST_BAD_STREAM; break; }
+                const BaseExtra dc = distance_code((uint32_t)ds);
+                uint32_t dist = dc.base;
+                if (dc.extra) dist += get_extra(b, s, lane, dc.extra);
+                if (dist > h.produced) { h.st = ST_BAD_STREAM; break; }
+                if (h.produced + len > isize) { h.st = ST_SIZE; break; }
+                uint8_t* dst = out + h.produced;
+                const uint8_t* src = dst - dist;
+                if (dist >= 8) {
+                    // source and destination do not overlap within a word: eight bytes per round trip.  The last word may
+                    // write up to seven bytes past the match — bytes this lane overwrites with its next symbols, or the
+                    // padding behind the member's stretch (the caller leaves 8 bytes)
+                    for (uint32_t i = 0; i < len; i += 8) *reinterpret_cast<u64_unaligned*>(dst + i) = *reinterpret_cast<const u64_unaligned*>(src + i);
                 } else {
-                    dist += bits_get(b, ex);
+                    for (uint32_t i = 0; i < len; ++i) dst[i] = src[i];
                 }
+                h.produced += len;
+                if (bits_used(b) > (uint64_t)in_len * 8) { h.st = ST_INPUT_END; break; }
             }
-            if (dist > produced) { st = ST_BAD_STREAM; break; }
-            if (produced + len > isize) { st = ST_SIZE; break; }
-            uint8_t* dst = out + produced;
-            const uint8_t* src = dst - dist;
-#ifdef SVX_EXP_INFL_NOCOPY  // ablation: what the match copies cost (output and CRC wrong)
-            if (false) {
-#else
-            if (dist >= 8) {
-#endif
-                // source and destination do not overlap within a word: eight bytes per round trip.  The last word may
-                // write up to seven bytes past the match — bytes this lane overwrites with its next symbols, or the
-                // padding behind the member's stretch (the caller leaves 8 bytes)
-                for (uint32_t i = 0; i < len; i += 8) *reinterpret_cast<u64_unaligned*>(dst + i) = *reinterpret_cast<const u64_unaligned*>(src + i);
-            } else {
-#ifndef SVX_EXP_INFL_NOCOPY
-                for (uint32_t i = 0; i < len; ++i) dst[i] = src[i];
-#endif
-            }
-            produced += len;
-            if (bits_used(b) > (uint64_t)in_len * 8) { st = ST_INPUT_END; break; }
         }
-        if (st == ST_OK && bits_used(b) > (uint64_t)in_len * 8) st = ST_INPUT_END;
-    }
+        if (h.st == ST_OK && bits_used(b) > (uint64_t)in_len * 8) h.st = ST_INPUT_END;
+    } while (!h.last && h.st == ST_OK);
+    const uint32_t produced = h.produced;
+    uint32_t st = h.st;
     // ---- CRC-32 of the member's bytes: a second pass over the lane's own output, four table look-ups per word
     uint32_t crc = 0xFFFFFFFFu;
     if (st == ST_OK && produced == isize) {
@@ -462,216 +561,15 @@ constexpr uint32_t kTokStride = SVX_INFLATE_TOK_STRIDE;
 constexpr uint32_t kTokFinal = 0xFFFFFFFFu;    // n_tok: the parse has ended the member with its status
 constexpr uint32_t kTokPending = 0xFFFFFFFEu;  // n_tok: k_inflate_wparse hands the member to k_inflate_parse
 
-constexpr int kRingBytes = 128;  // per member: 2 refills of 64 bytes
-struct ParseLds {
-    uint16_t tab_ll[1 << kLLBits][kLanes];
-    uint16_t tab_d[1 << kDBits][kLanes];
-    uint16_t cnt_ll[kMaxBits + 1][kLanes];
-    uint16_t cnt_d[kMaxBits + 1][kLanes];
-    uint16_t sym_ll[kLL][kLanes];
-    uint16_t sym_d[kDist][kLanes];
-    uint8_t lens4[(kLL + kDist + 2) / 2][kLanes];
-    uint32_t ring[kRingBytes / 4][kLanes];   // [word][member]: lanes reading the same word index hit different banks
-    uint32_t in_lo[kLanes], in_hi[kLanes], in_len[kLanes], ring_hi[kLanes], rd_pos[kLanes];  // what the refill lanes need of a member
-};
-// (the helpers above take the table struct as `Lds`: the same member names)
-__device__ __forceinline__ uint32_t len_get(const ParseLds& s, int i, int lane) { return (s.lens4[i >> 1][lane] >> (4 * (i & 1))) & 15u; }
-__device__ __forceinline__ void len_set(ParseLds& s, int i, int lane, uint32_t v) {
-    const uint32_t sh = 4 * (i & 1);
-    s.lens4[i >> 1][lane] = (uint8_t)((s.lens4[i >> 1][lane] & ~(15u << sh)) | ((v & 15u) << sh));
-}
-template <typename CNT, typename SYM>
-__device__ __forceinline__ int huff_construct_p(CNT cnt, SYM sym, const ParseLds& lds, int base, int n, int lane) {
-    for (int l = 0; l <= kMaxBits; ++l) cnt[l][lane] = 0;
-    for (int s = 0; s < n; ++s) cnt[len_get(lds, base + s, lane)][lane] += 1;
-    if (cnt[0][lane] == n) return 0;
-    int left = 1;
-    for (int l = 1; l <= kMaxBits; ++l) {
-        left <<= 1;
-        left -= cnt[l][lane];
-        if (left < 0) return left;
-    }
-    uint16_t offs[kMaxBits + 1];
-    offs[1] = 0;
-    for (int l = 1; l < kMaxBits; ++l) offs[l + 1] = offs[l] + cnt[l][lane];
-    for (int s = 0; s < n; ++s) {
-        const int l = (int)len_get(lds, base + s, lane);
-        if (l) sym[offs[l]++][lane] = (uint16_t)s;
-    }
-    return left;
-}
+using ParseLane = LaneState<RBits>;
 
-// The bit buffer of a member, fed from its LDS ring.  pos: input bytes taken into buf / next; the ring holds the input
-// bytes [.., ring_hi), zero behind the member's end.
-struct RBits {
-    uint64_t buf;
-    uint32_t cnt, pos, next, ring_hi, in_len;
-    const uint8_t* in;
-};
-// 64 more bytes into THIS lane's ring by the lane itself (block headers take their bits in long runs; the symbol loop
-// is topped up by the whole wave, parse_top_up)
-// (out of line, like the walk below and the block header: the symbol loop has to stay small enough for the instruction
-//  cache — inlined at every refill site the kernel was 150 KB of code and a step took 1 300 clocks)
-// (arguments by value: a reference would pin the caller's bit reader to scratch memory)
-__device__ __noinline__ void rb_fill_words(const uint8_t* in, uint32_t ring_hi, uint32_t in_len, ParseLds& s, int lane) {
-    uint32_t w[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { uint32_t real; w[k] = load_word(in, ring_hi + 4u * k, in_len, &real); }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s.ring[((ring_hi >> 2) + k) & (kRingBytes / 4 - 1)][lane] = w[k];
-}
-__device__ __forceinline__ void rb_fill_self(RBits& b, ParseLds& s, int lane) {
-    rb_fill_words(b.in, b.ring_hi, b.in_len, s, lane);
-    b.ring_hi += 64;
-}
-__device__ __forceinline__ void rb_refill(RBits& b, ParseLds& s, int lane) {
-    if (b.cnt <= 32) {
-        b.buf |= (uint64_t)b.next << b.cnt;
-        b.cnt += 32;
-        b.pos += 4;
-        if (b.pos + 4 > b.ring_hi) rb_fill_self(b, s, lane);
-        b.next = s.ring[(b.pos >> 2) & (kRingBytes / 4 - 1)][lane];
-    }
-}
-__device__ __forceinline__ uint32_t rb_get(RBits& b, ParseLds& s, int lane, uint32_t n) {  // n <= 16
-    rb_refill(b, s, lane);
-    const uint32_t v = (uint32_t)b.buf & ((1u << n) - 1u);
-    b.buf >>= n;
-    b.cnt -= n;
-    return v;
-}
-__device__ __forceinline__ uint64_t rb_used(const RBits& b) { return (uint64_t)b.pos * 8 - b.cnt; }
-
-// puff.c's decode() on the register-resident counts: the code-length code of a dynamic block's header, and the codes
-// the look-up tables do not hold (longer than 9 / 7 bits).  `sym`: the sorted symbols, [index][member].
-// Returns symbol << 8 | bits used, or -1.
-__device__ __noinline__ int rb_walk_cold(uint32_t bitbuf, const Counts c, const uint16_t (*sym)[kLanes], int lane) {
-    int code = 0, first = 0, index = 0;
-    for (int len = 1; len <= kMaxBits; ++len) {
-        code |= (int)(bitbuf & 1u);
-        bitbuf >>= 1;
-        const int count = (int)((c.w[len >> 1] >> (16 * (len & 1))) & 0xFFFFu);
-        if (code - count < first) return ((int)sym[index + (code - first)][lane] << 8) | len;
-        index += count;
-        first += count;
-        first <<= 1;
-        code <<= 1;
-    }
-    return -1;
-}
-template <typename SYM>
-__device__ __forceinline__ int rb_walk(RBits& b, ParseLds& s, const Counts& c, SYM sym, int lane) {
-    rb_refill(b, s, lane);
-    const int r = rb_walk_cold((uint32_t)b.buf, c, sym, lane);
-    if (r < 0) return -1;
-    b.buf >>= (uint32_t)r & 255u;
-    b.cnt -= (uint32_t)r & 255u;
-    return r >> 8;
-}
-template <int BITS, typename TAB, typename SYM>
-__device__ __forceinline__ int rb_decode(RBits& b, ParseLds& s, TAB tab, const Counts& c, SYM sym, int lane) {
-    rb_refill(b, s, lane);
-    const uint32_t e = tab[(uint32_t)b.buf & ((1u << BITS) - 1u)][lane];
-    if (__builtin_expect(e != 0u, 1)) {
-        const uint32_t len = e & 15u;
-        b.buf >>= len;
-        b.cnt -= len;
-        return (int)(e >> 4);
-    }
-    return rb_walk(b, s, c, sym, lane);  // (refills nothing: 32 bits are there)
-}
-
-enum { PS_HEADER = 0, PS_SYM = 1, PS_STORED = 2, PS_DONE = 3 };
-
-// what a member's lane carries through the parse
-struct ParseLane {
-    RBits b;
-    Counts c_ll, c_d;
-    uint32_t isize, produced, st, stored_left;
-    bool last;
-};
-
-// A block header: type, (for dynamic codes) the code lengths, the tables of the block.  Out of line — a few calls per
-// member, thousands of instructions.  Returns the lane's next state.
-__device__ __noinline__ int parse_header(ParseLane& h, ParseLds& s, const int lane) {
-    RBits& b = h.b;
-    h.last = rb_get(b, s, lane, 1) != 0;
-    const uint32_t type = rb_get(b, s, lane, 2);
-    if (type == 0) {  // stored: skip to the byte boundary, LEN / NLEN, raw bytes
-        const uint32_t drop = b.cnt & 7u;
-        b.buf >>= drop;
-        b.cnt -= drop;
-        const uint32_t len = rb_get(b, s, lane, 16), nlen = rb_get(b, s, lane, 16);
-        if ((len ^ 0xFFFFu) != nlen) { h.st = ST_BAD_STREAM; return PS_DONE; }
-        if (h.produced + len > h.isize) { h.st = ST_SIZE; return PS_DONE; }
-        h.stored_left = len;
-        return PS_STORED;
-    }
-    if (type == 3) { h.st = ST_BAD_STREAM; return PS_DONE; }
-    bool good = true;
-    if (type == 1) {  // fixed codes
-        for (int i = 0; i < 144; ++i) len_set(s, i, lane, 8);
-        for (int i = 144; i < 256; ++i) len_set(s, i, lane, 9);
-        for (int i = 256; i < 280; ++i) len_set(s, i, lane, 7);
-        for (int i = 280; i < kLL; ++i) len_set(s, i, lane, 8);
-        for (int i = 0; i < kDist; ++i) len_set(s, kLL + i, lane, 5);
-        huff_construct_p(s.cnt_ll, s.sym_ll, s, 0, kLL, lane);
-        huff_construct_p(s.cnt_d, s.sym_d, s, kLL, kDist, lane);
-    } else {  // dynamic codes (as in k_bgzf_inflate)
-        const uint32_t nlen = rb_get(b, s, lane, 5) + 257, ndist = rb_get(b, s, lane, 5) + 1, ncode = rb_get(b, s, lane, 4) + 4;
-        good = nlen <= 286 && ndist <= 30;
-        if (good) {
-            for (int i = 0; i < 19; ++i) len_set(s, i, lane, 0);
-            for (uint32_t i = 0; i < ncode; ++i) len_set(s, kClOrder[i], lane, rb_get(b, s, lane, 3));
-            good = huff_construct_p(s.cnt_d, s.sym_d, s, 0, 19, lane) == 0;  // (zlib: must be complete)
-        }
-        if (good) {
-            const Counts cl_counts = load_counts(s.cnt_d, lane);
-            uint32_t idx = 0;
-            while (good && idx < nlen + ndist) {
-                const int sym = rb_walk(b, s, cl_counts, s.sym_d, lane);
-                if (sym < 0) { good = false; }
-                else if (sym < 16) { len_set(s, (int)idx++, lane, (uint32_t)sym); }
-                else {
-                    uint32_t prev = 0, rep = 0;
-                    if (sym == 16) {
-                        if (idx == 0) good = false;
-                        else { prev = len_get(s, (int)idx - 1, lane); rep = 3 + rb_get(b, s, lane, 2); }
-                    } else if (sym == 17) {
-                        rep = 3 + rb_get(b, s, lane, 3);
-                    } else {
-                        rep = 11 + rb_get(b, s, lane, 7);
-                    }
-                    if (good && idx + rep > nlen + ndist) good = false;
-                    while (good && rep--) len_set(s, (int)idx++, lane, prev);
-                }
-            }
-        }
-        if (good) good = len_get(s, 256, lane) != 0;  // no end-of-block code
-        if (good) {
-            for (int i = (int)ndist - 1; i >= 0; --i) len_set(s, kLL + i, lane, len_get(s, (int)nlen + i, lane));
-            for (uint32_t i = nlen; i < (uint32_t)kLL; ++i) len_set(s, (int)i, lane, 0);
-            for (uint32_t i = ndist; i < (uint32_t)kDist; ++i) len_set(s, kLL + (int)i, lane, 0);
-            // incomplete code sets are allowed only when they consist of ONE code of length 1 (zlib inflate_table)
-            int err = huff_construct_p(s.cnt_ll, s.sym_ll, s, 0, kLL, lane);
-            if (err < 0 || (err > 0 && kLL != (int)s.cnt_ll[0][lane] + (int)s.cnt_ll[1][lane])) good = false;
-            if (good) {
-                err = huff_construct_p(s.cnt_d, s.sym_d, s, kLL, kDist, lane);
-                if (err < 0 || (err > 0 && kDist != (int)s.cnt_d[0][lane] + (int)s.cnt_d[1][lane])) good = false;
-            }
-        }
-    }
-    if (!good) { h.st = ST_BAD_STREAM; return PS_DONE; }
-    huff_table<kLLBits>(s.tab_ll, s.cnt_ll, s.sym_ll, lane);
-    huff_table<kDBits>(s.tab_d, s.cnt_d, s.sym_d, lane);
-    h.c_ll = load_counts(s.cnt_ll, lane);
-    h.c_d = load_counts(s.cnt_d, lane);
-    return PS_SYM;
-}
+// block_header out of line — a few calls per member, thousands of instructions.
+__device__ __noinline__ int parse_header(ParseLane& h, ParseLds& s, const int lane) { return block_header(h, s, lane); }
 
 __global__ __launch_bounds__(64) void k_inflate_parse(TwoPassArgs t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     ParseLds& s = *reinterpret_cast<ParseLds*>(lds_raw);
+    const HuffLds& ht = s.huff;
     const InfArgs& a = t.a;
     const int lane = (int)threadIdx.x;
     const uint32_t m = t.first + blockIdx.x * kLanes + (uint32_t)lane;
@@ -736,53 +634,37 @@ __global__ __launch_bounds__(64) void k_inflate_parse(TwoPassArgs t) {
             if (lane < kLanes && state != PS_DONE && b.ring_hi - b.pos <= 64u && b.ring_hi < b.in_len + 8u) b.ring_hi += 64;
         }
         if (state == PS_STORED) {
-            for (int k = 0; k < 4 && h.stored_left; ++k, --h.stored_left) out[h.produced++] = (uint8_t)rb_get(b, s, lane, 8);
+            for (int k = 0; k < 4 && h.stored_left; ++k, --h.stored_left) out[h.produced++] = (uint8_t)get_bits(b, s, lane, 8);
             if (h.stored_left == 0) {
-                if (rb_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
+                if (bits_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
                 else state = h.last ? PS_DONE : PS_HEADER;
             }
         }
         if (state == PS_SYM) {
-            const int sym = rb_decode<kLLBits>(b, s, s.tab_ll, h.c_ll, s.sym_ll, lane);
+            const int sym = huff_decode<kLLBits>(b, s, ht.tab_ll, h.c_ll, ht.sym_ll, lane);
             if (sym < 256) {
                 if (sym < 0) { h.st = ST_BAD_STREAM; state = PS_DONE; }
                 else if (h.produced >= h.isize) { h.st = ST_SIZE; state = PS_DONE; }
                 else out[h.produced++] = (uint8_t)sym;
             } else if (sym == 256) {
-                if (rb_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
+                if (bits_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
                 else state = h.last ? PS_DONE : PS_HEADER;
             } else {
                 const int li = sym - 257;
                 if (li >= 29) { h.st = ST_BAD_STREAM; state = PS_DONE; }
                 else {
-                    uint32_t len;
-                    if (li < 8) {
-                        len = 3u + (uint32_t)li;
-                    } else if (li == 28) {
-                        len = 258u;
-                    } else {
-                        const uint32_t e = ((uint32_t)li - 4u) >> 2;
-                        len = 3u + ((4u + ((uint32_t)li & 3u)) << e) + rb_get(b, s, lane, e);
-                    }
-                    const int ds = rb_decode<kDBits>(b, s, s.tab_d, h.c_d, s.sym_d, lane);
+                    const BaseExtra lc = length_code((uint32_t)li);
+                    uint32_t len = lc.base;
+                    if (lc.extra) len += get_bits(b, s, lane, lc.extra);
+                    const int ds = huff_decode<kDBits>(b, s, ht.tab_d, h.c_d, ht.sym_d, lane);
                     if (ds < 0 || ds >= 30) { h.st = ST_BAD_STREAM; state = PS_DONE; }
                     else {
-                        uint32_t dist;
-                        if (ds < 4) {
-                            dist = 1u + (uint32_t)ds;
-                        } else {
-                            const uint32_t ex = ((uint32_t)ds - 2u) >> 1;
-                            dist = 1u + ((2u + ((uint32_t)ds & 1u)) << ex);
-                            if (ex > 8) {  // up to 13 extra bits: two reads keep each within the refill guarantee
-                                const uint32_t lo = rb_get(b, s, lane, 8);
-                                dist += lo | (rb_get(b, s, lane, ex - 8) << 8);
-                            } else {
-                                dist += rb_get(b, s, lane, ex);
-                            }
-                        }
+                        const BaseExtra dc = distance_code((uint32_t)ds);
+                        uint32_t dist = dc.base;
+                        if (dc.extra) dist += get_extra(b, s, lane, dc.extra);
                         if (dist > h.produced) { h.st = ST_BAD_STREAM; state = PS_DONE; }
                         else if (h.produced + len > h.isize) { h.st = ST_SIZE; state = PS_DONE; }
-                        else if (rb_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
+                        else if (bits_used(b) > (uint64_t)b.in_len * 8) { h.st = ST_INPUT_END; state = PS_DONE; }
                         else {
                             tok[n_tok++] = make_uint2(h.produced | (len << 16), dist);  // (produced <= 65535, len <= 258)
                             h.produced += len;
