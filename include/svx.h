@@ -715,6 +715,26 @@ int svx_ctx_set_linkage_group_min(svx_ctx* ctx, uint32_t n);
 int svx_linkage_cut_batch_dev(svx_ctx* ctx, const double* d_dist, const uint32_t* n_members,
                               const uint32_t* d_n_members, uint32_t n_parts, double cutoff, uint32_t* d_labels);
 
+/*
+ * Interval containment, batched: does ONE interval of list l contain query window q, for every (l, q)?
+ * A key is contig << 32 | position.  List l owns the entries list_off[l] .. list_off[l+1] of start_key / end_key
+ * (list_off[0] = 0, n_lists + 1 offsets), with start_key non-decreasing inside the list; the end keys are in no order.
+ *     out[l * n_q + q] = 1  when list l holds an i with start_key[i] <= q_lo[q] and end_key[i] >= q_hi[q],
+ *                        0  otherwise
+ * — both bounds inclusive, and never the union of two intervals.  All pointers are HOST pointers; the call returns
+ * with `out` written.  SVX_E_INVALID (nothing launched, the context stays usable) for a list that is out of order, for
+ * an interval or a query whose two keys lie on different contigs, and for q_lo > q_hi.  n_lists == 0, n_q == 0 and
+ * empty lists are valid; an empty list answers 0 everywhere.
+ * Two launches: an inclusive prefix maximum of end_key inside every list (one workgroup per list,
+ * SVX_COVER_SCAN_CHUNK entries per pass, into the context workspace), then per (list, query) the upper bound of q_lo
+ * among the start keys and one compare with the prefix maximum in front of it — with the contig in the high word an
+ * interval of an earlier contig ends below every key of the query's contig, and one of a later contig is outside the
+ * prefix.
+ */
+#define SVX_COVER_SCAN_CHUNK 1024
+int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                    uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,32 @@ def _prepare(bam, options):
     return s
 
 
+def _coverage_of(s, ctx):
+    """(tid, start, end) of the records the loop visits (s.order: mapped, not secondary, mapq >= --min_mapq;
+    supplementary ones included), as int64 columns ordered by (tid, start) with ties in loop order: what
+    --keep_coverage persists (SVIM_MERGE.keep_coverage).  end = pos + ref_len of svx_cigar_stats, from the reader's own
+    copy of the CIGAR pool in HBM where there is one; a record without reference bases gives no interval."""
+    r = s.rec
+    if len(s.order) == 0:
+        return tuple(np.zeros(0, np.int64) for _ in range(3))
+    base = getattr(r, "base", None)
+    pool = base.device_pool(wait=True) if base is not None and hasattr(base, "device_pool") and r.cigar is base._cigar else None
+    if pool is not None:
+        ref_len = ctx.cigar_ref_len_dev(pool[0], int(r.cig_off[-1]), r.cig_off)
+    else:
+        ref_len = ctx.cigar_stats(r.cigar, np.asarray(r.cig_off, dtype=np.uint64))["ref_len"]
+    ref_len = np.asarray(ref_len, dtype=np.int64)[s.order]
+    tid = np.asarray(r.tid, dtype=np.int64)[s.order]
+    start = np.asarray(r.pos, dtype=np.int64)[s.order]
+    has = ref_len > 0
+    tid, start, end = tid[has], start[has], (start + ref_len)[has]
+    key = (tid << 32) | start
+    if len(key) > 1 and bool((key[1:] < key[:-1]).any()):  # (a view that ranks its contigs otherwise, an unsorted source)
+        o = np.argsort(key, kind="stable")
+        tid, start, end = tid[o], start[o], end[o]
+    return tid, start, end
+
+
 def _submit(samples, options, ctx):
     """ONE device submission for all `samples` (their headers agree): fills s.sig / s.raw / s.post / s.post_first
     with each sample's share of the results (record and segment indices local to the sample)."""
@@ -648,6 +674,10 @@ def collect_tables(bams, options, ctx=None):
     ctx = ctx or _lib.default_context(getattr(options, "device", 0) or 0)
     LAST_TIMING["context_wait_s"] = time.perf_counter() - t1
     t1 = time.perf_counter()
+    keep_coverage = bool(getattr(options, "keep_coverage", False))
+    if keep_coverage:
+        for s in samples:
+            s.coverage = _coverage_of(s, ctx)
     groups = _submission_groups(samples, _same_header(bams))
     for group in groups:
         _submit(group, options, ctx)
@@ -666,6 +696,9 @@ def collect_tables(bams, options, ctx=None):
     LAST_TIMING.update(load_s=t0 - tl, prepare_s=t1 - t0, submit_s=t2 - t1, tables_s=t3 - t2, sequences_wait_s=0.0,
                        load_cpu_s=c0 - cl, submit_and_tables_cpu_s=c3 - c0)
     tables = [_pending_sequences(s) for s in samples]
+    if keep_coverage:
+        for t, s in zip(tables, samples):
+            t.coverage = s.coverage  # (--keep_coverage: the caller writes it beside the sample's VCF)
     # The pool could stay pending until PAIR builds its byte pool (SVX_LAZY_SEQS=1: the decoding then runs beside
     # PAIR's keys, sort, windows and recipes).  Measured, interleaved on one box, four pairs of five runs: medians
     # 0.389-0.397 s pending vs 0.371-0.397 s waiting here — the host threads of the two sides compete for the same

@@ -47,6 +47,9 @@ _OUTPUT = [
                                                       "instead of variants.vcf")),
     ("--keep_candidates", dict(action="store_true", help="Also write the final candidate table as candidates.svxt into the "
                                                          "working directory: the input of svim-asm-merge")),
+    ("--keep_coverage", dict(action="store_true", help="Also write the reference intervals the assembly's alignments span "
+                                                       "as coverage.svxt into the working directory: what svim-asm-merge "
+                                                       "--genotype_non_carriers genotypes a non-carrier from")),
 ]
 
 

@@ -113,6 +113,7 @@ SEG_DTYPE = np.dtype([("q_start", "<i4"), ("q_end", "<i4"), ("ref_id", "<i4"), (
 HAP_PIECE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("repeat", "<u2"), ("flags", "<u2")])  # svx_hap_piece
 PIECE_UPPER, PIECE_REVCOMP = 1, 2
 LINKAGE_GROUP_LDS_N = 128        # SVX_LINKAGE_GROUP_LDS_N: largest partition whose working matrix the group kernel keeps in LDS
+COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 RAW_DTYPE = np.dtype([("kind", "<i4"), ("a0", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("a3", "<i4"),
                       ("a4", "<i4"), ("a5", "<i4"), ("pad", "<i4")])
@@ -180,6 +181,7 @@ SYMBOLS = {
     "svx_haplotype_distance_batch_mixed": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P]),
     "svx_pair_recipes": (C.c_int, [C.POINTER(RecipeIn), _P, _P, _P]),
     "svx_linkage_cut_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_double, _P]),
+    "svx_cover_query": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -507,6 +509,23 @@ class Context:
         self._check(self.lib.svx_cigar_stats(self.h, _ptr(cigar), _ptr(aln_off), n_aln, st))
         return out
 
+    def cigar_ref_len_dev(self, d_cigar, n_ops, aln_off):
+        """ref_len of cigar_stats for a CIGAR pool that is in HBM already (`d_cigar`: device address, complete —
+        a reader's svx_bam_device_pool after its wait): only the offsets go up and one word per alignment comes back."""
+        aln_off = _as(aln_off, np.uint64)
+        n_aln = len(aln_off) - 1 if len(aln_off) else 0
+        if n_aln == 0:
+            return np.zeros(0, np.uint32)
+        d_off, d_out = DeviceArray(self, aln_off), DeviceArray(self, nbytes=4 * n_aln)
+        try:
+            self._check(self.lib.svx_cigar_stats_dev(self.h, d_cigar, int(n_ops), d_off.ptr, n_aln,
+                                                     AlnStats(d_out.ptr, None, None, None, None)))
+            self.sync()
+            return d_out.download(np.uint32, n_aln)
+        finally:
+            d_off.free()
+            d_out.free()
+
     # ---------------------------------------------------------------- a3
     def segments_classify(self, segs, read_off, read_len, params):
         segs = np.ascontiguousarray(segs, dtype=SEG_DTYPE)
@@ -723,6 +742,26 @@ class Context:
             self._check(self.lib.svx_linkage_cut_batch(self.h, _ptr(dist), _ptr(n_members), len(n_members),
                                                        float(cutoff), _ptr(labels)))
         return labels
+
+    def cover_query(self, start_key, end_key, list_off, q_lo, q_hi):
+        """For every list l and query q: does ONE interval of the list contain the window [q_lo[q], q_hi[q]]?
+        Keys are contig << 32 | position; list l owns start_key / end_key[list_off[l]:list_off[l + 1]], sorted by
+        start key.  Returns uint8 [n_lists, n_q] (svx_cover_query)."""
+        start_key = _as(start_key, np.uint64)
+        end_key = _as(end_key, np.uint64)
+        list_off = _as(list_off, np.uint64)
+        q_lo = _as(q_lo, np.uint64)
+        q_hi = _as(q_hi, np.uint64)
+        if len(list_off) < 1 or len(start_key) != len(end_key) or len(q_lo) != len(q_hi) or \
+                int(list_off[-1]) != len(start_key):
+            raise SvxError(SVX_E_INVALID, "n_lists + 1 offsets ending at the number of intervals, one end per start, "
+                                          "one hi per lo")
+        n_lists, n_q = len(list_off) - 1, len(q_lo)
+        out = np.zeros((n_lists, n_q), np.uint8)
+        if n_lists and n_q:
+            self._check(self.lib.svx_cover_query(self.h, _ptr(start_key), _ptr(end_key), _ptr(list_off), n_lists,
+                                                 _ptr(q_lo), _ptr(q_hi), n_q, _ptr(out)))
+        return out
 
 
 def _cigar_text_args(text, rec_off):

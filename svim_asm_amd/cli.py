@@ -162,6 +162,11 @@ def main(arguments=None):
     if not options.sub:
         print("Please choose one of the two modes ('haploid' or 'diploid'). See --help for more information.")
         return
+    if getattr(options, "keep_coverage", False) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        # before any work: a rank holds the records of its own contigs only, and gathering them is a change of its own
+        print("svim-asm: --keep_coverage is not available in a sharded run (WORLD_SIZE={0}): every rank holds the alignments of "
+              "its own contigs only".format(os.environ["WORLD_SIZE"]), file=sys.stderr)
+        return 2
     distributed = _init_distributed(options)
     if not distributed:
         from svim_asm_amd import _warm
@@ -233,6 +238,7 @@ def _run_steps(options):
         if aln_file1 is None:
             return
         (sv_candidates,) = _collect([aln_file1], options)
+        per_haplotype = [sv_candidates]
     else:
         logging.info("MODE: diploid")
         logging.info("INPUT1: {0}".format(os.path.abspath(options.bam_file1)))
@@ -247,6 +253,7 @@ def _run_steps(options):
             return
         _timeline.mark("files open")
         sv_candidates1, sv_candidates2 = _collect([aln_file1, aln_file2], options)
+        per_haplotype = [sv_candidates1, sv_candidates2]
         if _timeline.enabled():
             from svim_asm_amd import SVIM_COLLECT
             _timeline.mark("COLLECT done", stages=dict(SVIM_COLLECT.LAST_TIMING))
@@ -295,6 +302,9 @@ def _run_steps(options):
     if getattr(options, "keep_candidates", False):
         from svim_asm_amd import SVIM_MERGE
         SVIM_MERGE.keep_candidates(sv_candidates, options.working_dir)
+    if getattr(options, "keep_coverage", False):
+        from svim_asm_amd import SVIM_MERGE
+        SVIM_MERGE.keep_coverage(aln_file1.references, aln_file1.lengths, [t.coverage for t in per_haplotype], options.working_dir)
     if _timeline.enabled():
         from svim_asm_amd import SVIM_COMBINE
         _timeline.mark("VCF written", stages={k: v for k, v in SVIM_COMBINE.LAST_TIMING.items() if k.startswith("vcf_")})

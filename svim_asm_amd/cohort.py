@@ -36,7 +36,11 @@ started by hand set SVX_NODE_PROCESSES themselves.
 it and, once every sample has returned 0, merges the tables into OUT_DIR/cohort.vcf with one genotype column per sample
 (svim-asm-merge, SVIM_MERGE.py): in this process on its default context, or — with `--gpus N` — in one more fresh child on the
 first listed device, started when all children have exited with 0; its status counts towards the parent's.  If a sample
-failed, no merge is attempted."""
+failed, no merge is attempted.
+
+`--keep_coverage` leaves every sample's coverage.svxt beside its VCF; `--merge OUT_DIR --genotype_non_carriers` implies it and
+passes the option (and `--genotype_margin N`) on to the merge, in the single process and to the merge child of `--gpus N`: the
+samples without a call in a record are then genotyped per haplotype from their assemblies' coverage."""
 import gc
 import logging
 import os
@@ -208,6 +212,9 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
         if getattr(o, "keep_candidates", False):
             from svim_asm_amd import SVIM_MERGE
             SVIM_MERGE.keep_candidates(candidates, wd)
+        if getattr(o, "keep_coverage", False):
+            from svim_asm_amd import SVIM_MERGE
+            SVIM_MERGE.keep_coverage(mine_files[0].references, mine_files[0].lengths, [t.coverage for t in mine], wd)
         _timeline.mark("VCF written", sample=first_no + k)
         logging.info("sample %d of %d: %s/variants.vcf%s", first_no + k + 1, n_total, wd, ".gz" if getattr(o, "bgzip_output", False) else "")
     for f in files:
@@ -246,14 +253,29 @@ def _take_merge(rest):
     return rest, out_dir
 
 
-def _merge_command(mode, out_dir, genome, sample_dirs, device, rest):
+def _take_genotype(rest):
+    """(rest without --genotype_non_carriers / --genotype_margin and, where the first was given, with --keep_coverage
+    once; the two as arguments of svim-asm-merge)."""
+    try:
+        rest, margin = _take_option(rest, "--genotype_margin", None)
+    except ValueError:
+        raise ValueError("--genotype_margin takes a number of bases")
+    wanted = "--genotype_non_carriers" in rest
+    rest = [a for a in rest if a != "--genotype_non_carriers"]
+    if wanted and "--keep_coverage" not in rest:
+        rest = rest + ["--keep_coverage"]
+    extra = (["--genotype_non_carriers"] if wanted else []) + (["--genotype_margin", str(margin)] if margin is not None else [])
+    return rest, extra
+
+
+def _merge_command(mode, out_dir, genome, sample_dirs, device, rest, extra=()):
     """argv of the merge child of `--gpus N --merge OUT_DIR`: svim-asm-merge with the options of `rest` it shares with
-    the samples' command (a seam like _child_command)."""
+    the samples' command (a seam like _child_command) and `extra`, its own (_take_genotype)."""
     for name in ("--cohort_workers", "--cohort_group", "--cohort_threads", "--cohort_lanes"):  # (this command's own)
         rest, _ = _take_option(rest, name, 0)
     o = parse_arguments(cli.__version__, [mode, out_dir] + ["-"] * (2 if mode == "diploid" else 1) + [genome] + list(rest))
     script = os.path.join(os.path.dirname(_entry_script()), "svim-asm-merge")
-    return [sys.executable, script, out_dir, genome] + list(sample_dirs) + ["--device", str(device)] + _merge_options(o)
+    return [sys.executable, script, out_dir, genome] + list(sample_dirs) + ["--device", str(device)] + _merge_options(o) + list(extra)
 
 
 def _merge_options(o):
@@ -317,6 +339,13 @@ def launch(mode, manifest, genome, rest):
         print("svim-asm-cohort: " + devices, file=sys.stderr)
         return 2
     rest, merge_dir = _take_merge(rest)  # (the children keep their tables; the merge is one more child, below)
+    try:
+        rest, genotype = _take_genotype(rest)
+        if genotype and merge_dir is None:
+            raise ValueError("--genotype_non_carriers and --genotype_margin are options of the merge: give --merge OUT_DIR")
+    except ValueError as e:
+        print("svim-asm-cohort: %s" % e, file=sys.stderr)
+        return 2
     samples = read_manifest(manifest, 2 if mode == "diploid" else 1)  # (a malformed manifest fails here, before any child exists)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
     shares = [(devices[k], share) for k, share in enumerate(deal(samples, len(devices))) if share]
@@ -360,7 +389,7 @@ def launch(mode, manifest, genome, rest):
         if merge_dir is not None and not caught:
             if len(procs) == len(shares) and all(p.returncode == 0 for p in procs):
                 # one more fresh child, alone on the first listed device: this process still never touches the GPU
-                merge_proc = subprocess.Popen(_merge_command(mode, merge_dir, genome, [wd for wd, _ in samples], devices[0], rest),
+                merge_proc = subprocess.Popen(_merge_command(mode, merge_dir, genome, [wd for wd, _ in samples], devices[0], rest, genotype),
                                               env=dict(os.environ, SVX_NODE_PROCESSES="1"))
                 procs.append(merge_proc)
                 wait_for_children()
@@ -409,6 +438,13 @@ def main(argv=None):
     rest, reader_threads = _take_option(rest, "--cohort_threads", 0)
     rest, lanes = _take_option(rest, "--cohort_lanes", 0)
     rest, merge_dir = _take_merge(rest)
+    try:
+        rest, genotype = _take_genotype(rest)
+        if genotype and merge_dir is None:
+            raise ValueError("--genotype_non_carriers and --genotype_margin are options of the merge: give --merge OUT_DIR")
+    except ValueError as e:
+        print("svim-asm-cohort: %s" % e, file=sys.stderr)
+        return 2
     samples = read_manifest(manifest, n_bams)
     _timeline.mark("cohort main")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)-7.7s]  %(message)s")
@@ -484,7 +520,7 @@ def main(argv=None):
         else:
             # the workers have joined and every sample returned 0: here, on the process's default context
             from svim_asm_amd import merge_cli
-            return merge_cli.main([merge_dir, genome] + [wd for wd, _ in samples] + ["--device", str(device)] + _merge_options(opts[0]))
+            return merge_cli.main([merge_dir, genome] + [wd for wd, _ in samples] + ["--device", str(device)] + _merge_options(opts[0]) + genotype)
     return state["rc"]
 
 

@@ -5,7 +5,11 @@ one VCF with a genotype column per sample (SVIM_MERGE.py).
     svim-asm-merge OUT_DIR GENOME --manifest MANIFEST [options]
 
 MANIFEST: a cohort manifest (svim-asm-cohort); its first column names the sample directories.  A sample's column is
-named after its directory; the records go to OUT_DIR/cohort.vcf (cohort.vcf.gz and its index with --bgzip_output)."""
+named after its directory; the records go to OUT_DIR/cohort.vcf (cohort.vcf.gz and its index with --bgzip_output).
+
+With --genotype_non_carriers a sample without a call in a record is genotyped per haplotype from the coverage its run
+kept (coverage.svxt, written with --keep_coverage): 0 where one alignment of the haplotype's assembly spans the record's
+window, . where none does."""
 import argparse
 import logging
 import os
@@ -32,6 +36,10 @@ def parse(argv):
     p.add_argument("--tandem_duplications_as_insertions", action="store_true", help="Represent tandem duplications as insertions")
     p.add_argument("--interspersed_duplications_as_insertions", action="store_true",
                    help="Represent interspersed duplications as insertions")
+    p.add_argument("--genotype_non_carriers", action="store_true",
+                   help="Genotype the samples without a call per haplotype (0 or .) from their coverage.svxt (--keep_coverage)")
+    p.add_argument("--genotype_margin", type=int, default=None,
+                   help="Bases on either side of a record an alignment has to span (default: --partition_max_distance)")
     p.add_argument("--bgzip_output", action="store_true", help="Write cohort.vcf.gz and its tabix index instead of cohort.vcf")
     p.add_argument("--device", type=int, default=0, help="HIP device index of the GPU to use")
     p.add_argument("--verbose", action="store_true", help="Enable more verbose logging")
@@ -72,6 +80,9 @@ def main(argv=None):
     try:
         tables = [SVIM_MERGE.read_candidates(d) for d in dirs]
         SVIM_MERGE.check_same_contigs(tables, names)
+        coverages = [SVIM_MERGE.read_coverage(d) for d in dirs] if options.genotype_non_carriers else None
+        if options.genotype_margin is not None and options.genotype_margin < 0:
+            raise ValueError("--genotype_margin %d: a number of bases, 0 or more" % options.genotype_margin)
     except ValueError as e:
         logging.error("%s", e)
         return 1
@@ -84,7 +95,14 @@ def main(argv=None):
     options.query_names = False
     merged, genotypes = SVIM_MERGE.merge_tables(tables, names, reference, options)
     types_to_output = [entry.strip() for entry in options.types.split(",")]
-    path = SVIM_MERGE.write_cohort_vcf(merged, genotypes, names, __version__, types_to_output, reference, options)
+    covered = None
+    if coverages is not None:
+        try:
+            covered = SVIM_MERGE.genotype_non_carriers(merged, coverages, options, sample_names=names)
+        except ValueError as e:
+            logging.error("%s", e)
+            return 1
+    path = SVIM_MERGE.write_cohort_vcf(merged, genotypes, names, __version__, types_to_output, reference, options, C=covered)
     logging.info("%d records of %d samples: %s", len(merged), len(names), path)
     return 0
 
