@@ -735,6 +735,27 @@ int svx_linkage_cut_batch_dev(svx_ctx* ctx, const double* d_dist, const uint32_t
 int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
                     uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out);
 
+/*
+ * Single coverage, batched: where does EXACTLY one entry of list l lie over the reference?  The lists are laid out as
+ * for svx_cover_query; an entry is the half-open key range [start_key, end_key).  With depth(p) the number of entries
+ * of the list with start <= p < end, the list's segments are the maximal ranges [a, b) on which depth is 1 and the one
+ * covering entry is the same entry throughout — two entries that abut give two abutting segments, never one —, in
+ * ascending order:
+ *     seg_lo / seg_hi[seg_off[l] .. seg_off[l+1])     the segments of list l, seg_off[0] = 0, contiguous over the lists
+ * The caller provides room for list_off[n_lists] segments (a list never has more segments than entries) and for
+ * n_lists + 1 offsets.  All pointers are HOST pointers; the call returns with seg_off and seg_off[n_lists] segments
+ * written.  SVX_E_INVALID (nothing launched, the context stays usable) for list_off[0] != 0, decreasing offsets, a list
+ * that is out of order, an entry whose two keys lie on different contigs and an entry with end <= start; the message
+ * names the list and the entry.  n_lists == 0 and empty lists are valid (seg_off[l+1] == seg_off[l]).
+ * Three launches.  With the entries in start order, slot k is [s_k, s_k+1), the last one open to the right; m1 >= m2
+ * being the two largest end keys of entries 0..k, depth is 1 inside the slot exactly on
+ * [max(s_k, m2), min(s_k+1, m1)): one workgroup per list scans (m1, m2) under "top two of the four",
+ * SVX_COVER_SCAN_CHUNK slots per pass, and compacts the non-empty candidates list-locally into the context workspace;
+ * an exclusive sum of the lists' counts gives seg_off; a third launch moves every list's segments to their place.
+ */
+int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                     uint32_t n_lists, uint64_t* seg_lo, uint64_t* seg_hi, uint64_t* seg_off);
+
 #ifdef __cplusplus
 }
 #endif

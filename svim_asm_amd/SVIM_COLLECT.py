@@ -674,7 +674,8 @@ def collect_tables(bams, options, ctx=None):
     ctx = ctx or _lib.default_context(getattr(options, "device", 0) or 0)
     LAST_TIMING["context_wait_s"] = time.perf_counter() - t1
     t1 = time.perf_counter()
-    keep_coverage = bool(getattr(options, "keep_coverage", False))
+    # (--callable_bed sweeps the same intervals: computed for either option, written as coverage.svxt for the first alone)
+    keep_coverage = bool(getattr(options, "keep_coverage", False) or getattr(options, "callable_bed", False))
     if keep_coverage:
         for s in samples:
             s.coverage = _coverage_of(s, ctx)
@@ -698,7 +699,7 @@ def collect_tables(bams, options, ctx=None):
     tables = [_pending_sequences(s) for s in samples]
     if keep_coverage:
         for t, s in zip(tables, samples):
-            t.coverage = s.coverage  # (--keep_coverage: the caller writes it beside the sample's VCF)
+            t.coverage = s.coverage  # (--keep_coverage, --callable_bed: the caller writes its files beside the sample's VCF)
     # The pool could stay pending until PAIR builds its byte pool (SVX_LAZY_SEQS=1: the decoding then runs beside
     # PAIR's keys, sort, windows and recipes).  Measured, interleaved on one box, four pairs of five runs: medians
     # 0.389-0.397 s pending vs 0.371-0.397 s waiting here — the host threads of the two sides compete for the same

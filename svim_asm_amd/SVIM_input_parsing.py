@@ -50,6 +50,11 @@ _OUTPUT = [
     ("--keep_coverage", dict(action="store_true", help="Also write the reference intervals the assembly's alignments span "
                                                        "as coverage.svxt into the working directory: what svim-asm-merge "
                                                        "--genotype_non_carriers genotypes a non-carrier from")),
+    ("--callable_bed", dict(action="store_true", help="Also write callable.bed into the working directory: the reference "
+                                                      "ranges that exactly one alignment of the assembly (diploid: of "
+                                                      "each haplotype's assembly) lies over")),
+    ("--callable_min_length", dict(type=int, default=0, help="Alignments with fewer reference bases than this are left "
+                                                             "out of --callable_bed (default: 0, none)")),
 ]
 
 

@@ -182,6 +182,7 @@ SYMBOLS = {
     "svx_pair_recipes": (C.c_int, [C.POINTER(RecipeIn), _P, _P, _P]),
     "svx_linkage_cut_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_double, _P]),
     "svx_cover_query": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
+    "svx_cover_single": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -762,6 +763,24 @@ class Context:
             self._check(self.lib.svx_cover_query(self.h, _ptr(start_key), _ptr(end_key), _ptr(list_off), n_lists,
                                                  _ptr(q_lo), _ptr(q_hi), n_q, _ptr(out)))
         return out
+
+    def cover_single(self, start_key, end_key, list_off):
+        """The ranges on which exactly ONE entry of a list — and the same one throughout — lies over the reference, per
+        list and in ascending order; entries are half-open [start_key, end_key), laid out as for cover_query.  Returns
+        (seg_lo, seg_hi, seg_off): uint64, list l's segments at [seg_off[l], seg_off[l + 1]) (svx_cover_single)."""
+        start_key = _as(start_key, np.uint64)
+        end_key = _as(end_key, np.uint64)
+        list_off = _as(list_off, np.uint64)
+        if len(list_off) < 1 or len(start_key) != len(end_key) or int(list_off[-1]) != len(start_key):
+            raise SvxError(SVX_E_INVALID, "n_lists + 1 offsets ending at the number of intervals, one end per start")
+        n_lists, n = len(list_off) - 1, len(start_key)
+        seg_lo, seg_hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        seg_off = np.zeros(n_lists + 1, np.uint64)
+        if n_lists:
+            self._check(self.lib.svx_cover_single(self.h, _ptr(start_key), _ptr(end_key), _ptr(list_off), n_lists,
+                                                  _ptr(seg_lo), _ptr(seg_hi), _ptr(seg_off)))
+        n_seg = int(seg_off[-1])
+        return seg_lo[:n_seg].copy(), seg_hi[:n_seg].copy(), seg_off
 
 
 def _cigar_text_args(text, rec_off):

@@ -167,6 +167,13 @@ def main(arguments=None):
         print("svim-asm: --keep_coverage is not available in a sharded run (WORLD_SIZE={0}): every rank holds the alignments of "
               "its own contigs only".format(os.environ["WORLD_SIZE"]), file=sys.stderr)
         return 2
+    if getattr(options, "callable_bed", False) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        print("svim-asm: --callable_bed is not available in a sharded run (WORLD_SIZE={0}): every rank holds the alignments of "
+              "its own contigs only".format(os.environ["WORLD_SIZE"]), file=sys.stderr)
+        return 2
+    if getattr(options, "callable_min_length", 0) < 0:
+        print("svim-asm: --callable_min_length {0}: a number of bases, 0 or more".format(options.callable_min_length), file=sys.stderr)
+        return 2
     distributed = _init_distributed(options)
     if not distributed:
         from svim_asm_amd import _warm
@@ -305,6 +312,9 @@ def _run_steps(options):
     if getattr(options, "keep_coverage", False):
         from svim_asm_amd import SVIM_MERGE
         SVIM_MERGE.keep_coverage(aln_file1.references, aln_file1.lengths, [t.coverage for t in per_haplotype], options.working_dir)
+    if getattr(options, "callable_bed", False):
+        from svim_asm_amd import SVIM_CALLABLE
+        SVIM_CALLABLE.write_sample_bed(aln_file1.references, [t.coverage for t in per_haplotype], options, options.working_dir)
     if _timeline.enabled():
         from svim_asm_amd import SVIM_COMBINE
         _timeline.mark("VCF written", stages={k: v for k, v in SVIM_COMBINE.LAST_TIMING.items() if k.startswith("vcf_")})

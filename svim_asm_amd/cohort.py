@@ -40,7 +40,11 @@ failed, no merge is attempted.
 
 `--keep_coverage` leaves every sample's coverage.svxt beside its VCF; `--merge OUT_DIR --genotype_non_carriers` implies it and
 passes the option (and `--genotype_margin N`) on to the merge, in the single process and to the merge child of `--gpus N`: the
-samples without a call in a record are then genotyped per haplotype from their assemblies' coverage."""
+samples without a call in a record are then genotyped per haplotype from their assemblies' coverage.
+
+`--callable_bed` (with `--callable_min_length N`) leaves every sample's callable.bed beside its VCF — the ranges exactly one
+alignment per haplotype lies over —, also under `--gpus N`; with `--merge OUT_DIR` it implies `--keep_coverage` and is passed on
+to the merge, which writes OUT_DIR/cohort.callable.bed with the number of samples per range."""
 import gc
 import logging
 import os
@@ -215,6 +219,9 @@ def run_group(mode, group, genome, get_ctx, first_no, n_total, workers=1, reader
         if getattr(o, "keep_coverage", False):
             from svim_asm_amd import SVIM_MERGE
             SVIM_MERGE.keep_coverage(mine_files[0].references, mine_files[0].lengths, [t.coverage for t in mine], wd)
+        if getattr(o, "callable_bed", False):
+            from svim_asm_amd import SVIM_CALLABLE
+            SVIM_CALLABLE.write_sample_bed(mine_files[0].references, [t.coverage for t in mine], o, wd, ctx=ctx)
         _timeline.mark("VCF written", sample=first_no + k)
         logging.info("sample %d of %d: %s/variants.vcf%s", first_no + k + 1, n_total, wd, ".gz" if getattr(o, "bgzip_output", False) else "")
     for f in files:
@@ -266,6 +273,21 @@ def _take_genotype(rest):
         rest = rest + ["--keep_coverage"]
     extra = (["--genotype_non_carriers"] if wanted else []) + (["--genotype_margin", str(margin)] if margin is not None else [])
     return rest, extra
+
+
+def _take_callable(rest, merging):
+    """--callable_bed and --callable_min_length stay in `rest`: every sample writes its callable.bed.  With a merge and the
+    first of them, (rest with --keep_coverage once, the two as arguments of svim-asm-merge); else (rest, [])."""
+    rest = list(rest)
+    if not merging or "--callable_bed" not in rest:
+        return rest, []
+    try:
+        _, min_length = _take_option(rest, "--callable_min_length", None)
+    except ValueError:
+        raise ValueError("--callable_min_length takes a number of bases")
+    if "--keep_coverage" not in rest:
+        rest = rest + ["--keep_coverage"]
+    return rest, ["--callable_bed"] + (["--callable_min_length", str(min_length)] if min_length is not None else [])
 
 
 def _merge_command(mode, out_dir, genome, sample_dirs, device, rest, extra=()):
@@ -343,6 +365,8 @@ def launch(mode, manifest, genome, rest):
         rest, genotype = _take_genotype(rest)
         if genotype and merge_dir is None:
             raise ValueError("--genotype_non_carriers and --genotype_margin are options of the merge: give --merge OUT_DIR")
+        rest, callable_bed = _take_callable(rest, merge_dir is not None)
+        genotype = genotype + callable_bed  # (the merge's own options, one list)
     except ValueError as e:
         print("svim-asm-cohort: %s" % e, file=sys.stderr)
         return 2
@@ -442,6 +466,8 @@ def main(argv=None):
         rest, genotype = _take_genotype(rest)
         if genotype and merge_dir is None:
             raise ValueError("--genotype_non_carriers and --genotype_margin are options of the merge: give --merge OUT_DIR")
+        rest, callable_bed = _take_callable(rest, merge_dir is not None)
+        genotype = genotype + callable_bed  # (the merge's own options, one list)
     except ValueError as e:
         print("svim-asm-cohort: %s" % e, file=sys.stderr)
         return 2

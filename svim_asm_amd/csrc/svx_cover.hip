@@ -17,6 +17,19 @@
 //                   maximum in front of it, one byte out — consecutive lanes, consecutive bytes.
 // Every word of the prefix maxima is written by the scan before the search reads it, and only inside the lists'
 // ranges: nothing depends on what the workspace held (the scratch contract, include/svx.h).
+//
+// svx_cover_single asks of the same lists where EXACTLY one entry lies over the reference: the maximal
+// ranges on which one entry, and the same one, is the only one with start <= p < end.  With the entries in start order
+// slot k is [s_k, s_k+1) (the last one open to the right); only entries 0..k can be active inside it, so with
+// m1 >= m2 the two largest end keys of the prefix 0..k the depth is 1 on [max(s_k, m2), min(s_k+1, m1)) and nowhere
+// else in the slot: at most one segment per slot, no sort, contig borders for free as above.  Three launches:
+//   k_single_scan     one workgroup per list, kChunk slots per pass: the inclusive scan of (m1, m2) under "top two of
+//                     the four" on the same ladder — NOT idempotent, so every combine is over disjoint lane ranges —,
+//                     one candidate segment per slot, a flag, the workgroup's exclusive sum of the flags with a running
+//                     count, the segments compacted list-locally into the workspace at list_off[l] + rank; the count;
+//   k_single_offsets  one workgroup: seg_off = exclusive sum of the counts over the lists;
+//   k_single_pack     every list's segments to their final contiguous place.
+// A list's pack reads the `count` words its scan wrote and nothing else.
 #include "svx_internal.h"
 
 namespace {
@@ -27,7 +40,8 @@ constexpr int kWaves = kThreads / 64;
 static_assert(kPer * kThreads == SVX_COVER_SCAN_CHUNK && kPer == 4, "four elements per thread, loaded as two 16-byte words");
 constexpr uint32_t kMaxGridY = 65535;
 
-// DPP lane movement (gfx9 family): 0 flows into lanes without a source — the identity of max over unsigned keys
+// DPP lane movement (gfx9 family): 0 flows into lanes without a source — the identity of max over unsigned keys, of
+// the sum, and (as a pair) of the top two
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xF, false);
@@ -35,16 +49,42 @@ __device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
     return (uint64_t)hi << 32 | lo;
 }
 __device__ __forceinline__ uint64_t max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-// inclusive maximum over the lanes 0..l of the wave
-__device__ __forceinline__ uint64_t wave_scan_max(uint64_t v) {
-    v = max64(v, dpp0_64<0x111, 0xF>(v));  // row_shr:1
-    v = max64(v, dpp0_64<0x112, 0xF>(v));  // row_shr:2
-    v = max64(v, dpp0_64<0x114, 0xF>(v));  // row_shr:4
-    v = max64(v, dpp0_64<0x118, 0xF>(v));  // row_shr:8
-    v = max64(v, dpp0_64<0x142, 0xA>(v));  // row_bcast:15 into rows 1 and 3
-    v = max64(v, dpp0_64<0x143, 0xC>(v));  // row_bcast:31 into rows 2 and 3
+__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+// the two largest end keys of a set of entries, m1 >= m2; (0, 0): no entry
+struct Top2 {
+    uint64_t m1, m2;
+};
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t dpp0(uint64_t v) { return dpp0_64<CTRL, ROW_MASK>(v); }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ Top2 dpp0(Top2 v) { return Top2{dpp0_64<CTRL, ROW_MASK>(v.m1), dpp0_64<CTRL, ROW_MASK>(v.m2)}; }
+struct OpMax {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return max64(a, b); }
+};
+struct OpAdd {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
+};
+// top two of the four: an element folded in twice would read as depth 2 — disjoint operands only
+struct OpTop2 {
+    __device__ __forceinline__ Top2 operator()(Top2 a, Top2 b) const {
+        return Top2{max64(a.m1, b.m1), max64(min64(a.m1, b.m1), max64(a.m2, b.m2))};
+    }
+};
+// inclusive scan over the lanes 0..l of the wave; 0 is op's identity.  Every step combines two DISJOINT lane ranges
+// (row_shr:n the n lanes in front of the 2^k a lane holds, row_bcast the whole rows in front), rows a step's mask leaves
+// out and lanes without a source combine with 0: op need not be idempotent.
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_scan(T v, Op op) {
+    v = op(v, dpp0<0x111, 0xF>(v));  // row_shr:1
+    v = op(v, dpp0<0x112, 0xF>(v));  // row_shr:2
+    v = op(v, dpp0<0x114, 0xF>(v));  // row_shr:4
+    v = op(v, dpp0<0x118, 0xF>(v));  // row_shr:8
+    v = op(v, dpp0<0x142, 0xA>(v));  // row_bcast:15 into rows 1 and 3
+    v = op(v, dpp0<0x143, 0xC>(v));  // row_bcast:31 into rows 2 and 3
     return v;
 }
+// inclusive maximum over the lanes 0..l of the wave
+__device__ __forceinline__ uint64_t wave_scan_max(uint64_t v) { return wave_scan(v, OpMax()); }
 
 __global__ __launch_bounds__(kThreads) void k_cover_scan(const uint64_t* __restrict__ end_key, const uint64_t* __restrict__ list_off,
                                                          uint64_t* __restrict__ pmax) {
@@ -100,6 +140,148 @@ __global__ __launch_bounds__(kThreads) void k_cover_search(const uint64_t* __res
     }
 }
 
+// Exclusive prefix of a lane's inclusive wave scan `incl` over the whole workgroup: the lanes in front of it in its wave
+// (wave_shr:1, lane 0 receives 0), the waves in front through `s_w`, and `total` of all four waves.  One barrier; the
+// caller keeps a second one between two uses of the same `s_w`.
+template <typename T, typename Op>
+__device__ __forceinline__ T group_before(T incl, T* s_w, int tid, Op op, T* total) {
+    const int wave = tid >> 6;
+    if ((tid & 63) == 63) s_w[wave] = incl;
+    T before = dpp0<0x138, 0xF>(incl);
+    __syncthreads();
+    T all = s_w[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+        if (w == wave) before = op(before, all);  // (waves 0..w-1, disjoint from this wave's lanes)
+        all = op(all, s_w[w]);
+    }
+    *total = all;
+    return before;
+}
+
+__global__ __launch_bounds__(kThreads) void k_single_scan(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ end_key,
+                                                          const uint64_t* __restrict__ list_off, uint64_t* __restrict__ loc_lo,
+                                                          uint64_t* __restrict__ loc_hi, uint64_t* __restrict__ count) {
+    __shared__ Top2 s_top[kWaves];
+    __shared__ uint64_t s_cnt[kWaves];
+    const uint64_t lo = list_off[blockIdx.x], hi = list_off[blockIdx.x + 1];
+    const int tid = (int)threadIdx.x;
+    Top2 carry = Top2{0, 0};
+    uint64_t written = 0;
+    // (the trip count depends on the list alone: every lane of the group takes every pass, DPP and barriers included;
+    //  s_top is written in front of the first barrier of a pass and read between the two, s_cnt written between them and
+    //  read behind the second: whoever writes either again has passed the barrier behind its last read)
+    for (uint64_t base = lo; base < hi; base += SVX_COVER_SCAN_CHUNK) {
+        const uint64_t first = base + (uint64_t)tid * kPer;
+        // slot j is [s[j], s[j + 1]): one start more than entries, UINT64_MAX behind the list's last
+        uint64_t s[kPer + 1];
+        Top2 t[kPer];
+#pragma unroll
+        for (int j = 0; j <= kPer; ++j) s[j] = first + j < hi ? start_key[first + j] : UINT64_MAX;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) t[j] = Top2{first + j < hi ? end_key[first + j] : 0, 0};
+#pragma unroll
+        for (int j = 1; j < kPer; ++j) t[j] = OpTop2()(t[j], t[j - 1]);
+        Top2 total;
+        Top2 before = group_before(wave_scan(t[kPer - 1], OpTop2()), s_top, tid, OpTop2(), &total);
+        before = OpTop2()(before, carry);
+        carry = OpTop2()(carry, total);
+        uint64_t seg_lo[kPer], seg_hi[kPer];
+        uint32_t mine = 0;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const Top2 m = OpTop2()(t[j], before);
+            seg_lo[j] = max64(s[j], m.m2);
+            seg_hi[j] = min64(s[j + 1], m.m1);
+            if (first + j >= hi) seg_hi[j] = 0;  // (no slot: seg_lo is UINT64_MAX there)
+            mine += seg_lo[j] < seg_hi[j] ? 1u : 0u;
+        }
+        uint64_t flagged;
+        uint64_t rank = group_before(wave_scan((uint64_t)mine, OpAdd()), s_cnt, tid, OpAdd(), &flagged);
+        // list-local: rank <= the slot's own index, so the stores stay inside [lo, hi)
+        rank += lo + written;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (seg_lo[j] < seg_hi[j]) {
+                loc_lo[rank] = seg_lo[j];
+                loc_hi[rank] = seg_hi[j];
+                ++rank;
+            }
+        written += flagged;
+    }
+    if (tid == 0) count[blockIdx.x] = written;
+}
+
+// seg_off[0] = 0, seg_off[l + 1] = count[0] + .. + count[l]: one workgroup, kChunk lists per pass
+__global__ __launch_bounds__(kThreads) void k_single_offsets(const uint64_t* __restrict__ count, uint32_t n_lists,
+                                                             uint64_t* __restrict__ seg_off) {
+    __shared__ uint64_t s_cnt[kWaves];
+    const int tid = (int)threadIdx.x;
+    uint64_t carry = 0;
+    if (tid == 0) seg_off[0] = 0;
+    for (uint32_t base = 0; base < n_lists; base += SVX_COVER_SCAN_CHUNK) {
+        const uint32_t first = base + (uint32_t)tid * kPer;
+        uint64_t v[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) v[j] = first + j < n_lists ? count[first + j] : 0;
+#pragma unroll
+        for (int j = 1; j < kPer; ++j) v[j] += v[j - 1];
+        uint64_t total;
+        const uint64_t before = group_before(wave_scan(v[kPer - 1], OpAdd()), s_cnt, tid, OpAdd(), &total) + carry;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (first + j < n_lists) seg_off[first + j + 1] = v[j] + before;
+        carry += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_single_pack(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ seg_off,
+                                                          const uint64_t* __restrict__ loc_lo, const uint64_t* __restrict__ loc_hi,
+                                                          uint64_t* __restrict__ seg_lo, uint64_t* __restrict__ seg_hi) {
+    const uint64_t from = list_off[blockIdx.x], to = seg_off[blockIdx.x], n = seg_off[blockIdx.x + 1] - to;
+    for (uint64_t i = (uint64_t)blockIdx.y * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.y * kThreads) {
+        seg_lo[to + i] = loc_lo[from + i];
+        seg_hi[to + i] = loc_hi[from + i];
+    }
+}
+
+constexpr uint32_t kPackGridY = 4;
+constexpr uint32_t kMaxGridX = 0x7FFFFFFFu;
+
+// What both entries require of their lists (host pointers): offsets from 0 that never decrease, every list sorted by
+// start key, every entry on one contig — and, for the entry that asks, no entry with end <= start.
+int check_lists(svx_ctx* ctx, const char* who, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                uint32_t n_lists, bool refuse_empty) {
+    if (list_off[0] != 0) {
+        SVX_SET_ERR(ctx, "%s: list_off[0] is %llu, not 0", who, (unsigned long long)list_off[0]);
+        return SVX_E_INVALID;
+    }
+    for (uint32_t l = 0; l < n_lists; ++l)
+        if (list_off[l + 1] < list_off[l]) {
+            SVX_SET_ERR(ctx, "%s: list_off decreases at list %u", who, l);
+            return SVX_E_INVALID;
+        }
+    if (list_off[n_lists] && (!start_key || !end_key)) return SVX_E_INVALID;
+    for (uint32_t l = 0; l < n_lists; ++l)
+        for (uint64_t i = list_off[l]; i < list_off[l + 1]; ++i) {
+            if (i > list_off[l] && start_key[i] < start_key[i - 1]) {
+                SVX_SET_ERR(ctx, "%s: list %u is not sorted by start key at entry %llu", who, l, (unsigned long long)(i - list_off[l]));
+                return SVX_E_INVALID;
+            }
+            if ((start_key[i] >> 32) != (end_key[i] >> 32)) {
+                SVX_SET_ERR(ctx, "%s: entry %llu of list %u starts and ends on different contigs", who,
+                            (unsigned long long)(i - list_off[l]), l);
+                return SVX_E_INVALID;
+            }
+            if (refuse_empty && end_key[i] <= start_key[i]) {
+                SVX_SET_ERR(ctx, "%s: entry %llu of list %u ends at or in front of its start", who, (unsigned long long)(i - list_off[l]), l);
+                return SVX_E_INVALID;
+            }
+        }
+    return SVX_OK;
+}
+
 }  // namespace
 
 extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
@@ -107,30 +289,9 @@ extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const ui
     if (!ctx) return SVX_E_INVALID;
     if (n_lists == 0 || n_q == 0) return SVX_OK;
     if (!list_off || !q_lo || !q_hi || !out) return SVX_E_INVALID;
-    if (list_off[0] != 0) {
-        SVX_SET_ERR(ctx, "svx_cover_query: list_off[0] is %llu, not 0", (unsigned long long)list_off[0]);
-        return SVX_E_INVALID;
-    }
-    for (uint32_t l = 0; l < n_lists; ++l)
-        if (list_off[l + 1] < list_off[l]) {
-            SVX_SET_ERR(ctx, "svx_cover_query: list_off decreases at list %u", l);
-            return SVX_E_INVALID;
-        }
+    int rc = check_lists(ctx, "svx_cover_query", start_key, end_key, list_off, n_lists, false);
+    if (rc != SVX_OK) return rc;
     const uint64_t n = list_off[n_lists];
-    if (n && (!start_key || !end_key)) return SVX_E_INVALID;
-    for (uint32_t l = 0; l < n_lists; ++l)
-        for (uint64_t i = list_off[l]; i < list_off[l + 1]; ++i) {
-            if (i > list_off[l] && start_key[i] < start_key[i - 1]) {
-                SVX_SET_ERR(ctx, "svx_cover_query: list %u is not sorted by start key at entry %llu", l,
-                            (unsigned long long)(i - list_off[l]));
-                return SVX_E_INVALID;
-            }
-            if ((start_key[i] >> 32) != (end_key[i] >> 32)) {
-                SVX_SET_ERR(ctx, "svx_cover_query: entry %llu of list %u starts and ends on different contigs",
-                            (unsigned long long)(i - list_off[l]), l);
-                return SVX_E_INVALID;
-            }
-        }
     for (uint32_t q = 0; q < n_q; ++q) {
         if ((q_lo[q] >> 32) != (q_hi[q] >> 32)) {
             SVX_SET_ERR(ctx, "svx_cover_query: query %u starts and ends on different contigs", q);
@@ -147,7 +308,7 @@ extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const ui
         return SVX_OK;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_stage_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8) + 2 * svx_take_bytes(n_q, 8) +
+    rc = svx_stage_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8) + 2 * svx_take_bytes(n_q, 8) +
                                         svx_take_bytes(n_out, 1));
     if (rc != SVX_OK) return rc;
     rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8));
@@ -179,5 +340,71 @@ extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const ui
     if (rc != SVX_OK) return rc;
     SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out, hipMemcpyDeviceToHost, ctx->stream));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVX_OK;
+}
+
+extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                                uint32_t n_lists, uint64_t* seg_lo, uint64_t* seg_hi, uint64_t* seg_off) {
+    if (!ctx || !seg_off) return SVX_E_INVALID;
+    seg_off[0] = 0;
+    if (n_lists == 0) return SVX_OK;
+    if (!list_off) return SVX_E_INVALID;
+    int rc = check_lists(ctx, "svx_cover_single", start_key, end_key, list_off, n_lists, true);
+    if (rc != SVX_OK) return rc;
+    const uint64_t n = list_off[n_lists];
+    if (n == 0) {  // empty lists only
+        memset(seg_off, 0, ((size_t)n_lists + 1) * 8);
+        return SVX_OK;
+    }
+    if (!seg_lo || !seg_hi) return SVX_E_INVALID;
+    if (n_lists > kMaxGridX) {
+        SVX_SET_ERR(ctx, "svx_cover_single: %u lists, at most %u", n_lists, kMaxGridX);
+        return SVX_E_TOO_LARGE;
+    }
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    rc = svx_stage_reserve(ctx, 4 * svx_take_bytes(n, 8) + 2 * svx_take_bytes((size_t)n_lists + 1, 8));
+    if (rc != SVX_OK) return rc;
+    rc = svx_ws_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes(n_lists, 8));
+    if (rc != SVX_OK) return rc;
+    uint64_t* d_start = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_end = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    uint64_t* d_seg_lo = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_seg_hi = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_seg_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    uint64_t* d_loc_lo = svx_ws_take<uint64_t>(ctx, n);
+    uint64_t* d_loc_hi = svx_ws_take<uint64_t>(ctx, n);
+    uint64_t* d_count = svx_ws_take<uint64_t>(ctx, n_lists);
+    SVX_HIP(ctx, hipMemcpyAsync(d_start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = svx_timing_begin(ctx);
+    if (rc != SVX_OK) return rc;
+    rc = svx_timing_mark(ctx, 1);
+    if (rc != SVX_OK) return rc;
+    hipLaunchKernelGGL(k_single_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d_start, d_end, d_off, d_loc_lo, d_loc_hi, d_count);
+    SVX_HIP(ctx, hipGetLastError());
+    rc = svx_timing_mark(ctx, 2);
+    if (rc != SVX_OK) return rc;
+    hipLaunchKernelGGL(k_single_offsets, dim3(1), dim3(kThreads), 0, ctx->stream, d_count, n_lists, d_seg_off);
+    SVX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_single_pack, dim3(n_lists, kPackGridY), dim3(kThreads), 0, ctx->stream, d_off, d_seg_off, d_loc_lo, d_loc_hi,
+                       d_seg_lo, d_seg_hi);
+    SVX_HIP(ctx, hipGetLastError());
+    rc = svx_timing_end(ctx);
+    if (rc != SVX_OK) return rc;
+    // the offsets first: they say how many segments there are to fetch
+    SVX_HIP(ctx, hipMemcpyAsync(seg_off, d_seg_off, ((size_t)n_lists + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t n_seg = seg_off[n_lists];
+    if (n_seg > n) {  // (cannot happen: at most one segment per slot)
+        SVX_SET_ERR(ctx, "svx_cover_single: %llu segments of %llu entries", (unsigned long long)n_seg, (unsigned long long)n);
+        return SVX_E_HIP;
+    }
+    if (n_seg) {
+        SVX_HIP(ctx, hipMemcpyAsync(seg_lo, d_seg_lo, n_seg * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_HIP(ctx, hipMemcpyAsync(seg_hi, d_seg_hi, n_seg * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return SVX_OK;
 }

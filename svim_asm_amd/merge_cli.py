@@ -9,13 +9,16 @@ named after its directory; the records go to OUT_DIR/cohort.vcf (cohort.vcf.gz a
 
 With --genotype_non_carriers a sample without a call in a record is genotyped per haplotype from the coverage its run
 kept (coverage.svxt, written with --keep_coverage): 0 where one alignment of the haplotype's assembly spans the record's
-window, . where none does."""
+window, . where none does.
+
+With --callable_bed the same files give OUT_DIR/cohort.callable.bed: contig, start, end and the number of samples whose
+own callable set — the ranges exactly one alignment per haplotype lies over — contains the range."""
 import argparse
 import logging
 import os
 import sys
 
-from svim_asm_amd import SVIM_MERGE
+from svim_asm_amd import SVIM_CALLABLE, SVIM_MERGE
 from svim_asm_amd.fasta import BgzfFormatError, FastaFile, MissingGziError
 
 __version__ = "1.0.3"
@@ -40,6 +43,11 @@ def parse(argv):
                    help="Genotype the samples without a call per haplotype (0 or .) from their coverage.svxt (--keep_coverage)")
     p.add_argument("--genotype_margin", type=int, default=None,
                    help="Bases on either side of a record an alignment has to span (default: --partition_max_distance)")
+    p.add_argument("--callable_bed", action="store_true",
+                   help="Also write cohort.callable.bed: the ranges exactly one alignment per haplotype lies over, with the number "
+                        "of samples, from the samples' coverage.svxt (--keep_coverage)")
+    p.add_argument("--callable_min_length", type=int, default=0,
+                   help="Alignments with fewer reference bases than this are left out of --callable_bed (default: 0, none)")
     p.add_argument("--bgzip_output", action="store_true", help="Write cohort.vcf.gz and its tabix index instead of cohort.vcf")
     p.add_argument("--device", type=int, default=0, help="HIP device index of the GPU to use")
     p.add_argument("--verbose", action="store_true", help="Enable more verbose logging")
@@ -80,7 +88,8 @@ def main(argv=None):
     try:
         tables = [SVIM_MERGE.read_candidates(d) for d in dirs]
         SVIM_MERGE.check_same_contigs(tables, names)
-        coverages = [SVIM_MERGE.read_coverage(d) for d in dirs] if options.genotype_non_carriers else None
+        coverages = [SVIM_MERGE.read_coverage(d) for d in dirs] if options.genotype_non_carriers or options.callable_bed else None
+        SVIM_CALLABLE.check_min_length(options)
         if options.genotype_margin is not None and options.genotype_margin < 0:
             raise ValueError("--genotype_margin %d: a number of bases, 0 or more" % options.genotype_margin)
     except ValueError as e:
@@ -96,14 +105,23 @@ def main(argv=None):
     merged, genotypes = SVIM_MERGE.merge_tables(tables, names, reference, options)
     types_to_output = [entry.strip() for entry in options.types.split(",")]
     covered = None
-    if coverages is not None:
+    if options.genotype_non_carriers:
         try:
             covered = SVIM_MERGE.genotype_non_carriers(merged, coverages, options, sample_names=names)
         except ValueError as e:
             logging.error("%s", e)
             return 1
+    if options.callable_bed:
+        try:
+            SVIM_MERGE.check_coverage_contigs(merged, coverages, names)
+            bed = SVIM_CALLABLE.write_cohort_bed(merged.contigs, coverages, options, options.working_dir, sample_names=names)
+        except ValueError as e:
+            logging.error("%s", e)
+            return 1
     path = SVIM_MERGE.write_cohort_vcf(merged, genotypes, names, __version__, types_to_output, reference, options, C=covered)
     logging.info("%d records of %d samples: %s", len(merged), len(names), path)
+    if options.callable_bed:
+        logging.info("callable ranges of %d samples: %s", len(names), bed)
     return 0
 
 
