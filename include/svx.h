@@ -716,6 +716,30 @@ int svx_linkage_cut_batch_dev(svx_ctx* ctx, const double* d_dist, const uint32_t
                               const uint32_t* d_n_members, uint32_t n_parts, double cutoff, uint32_t* d_labels);
 
 /*
+ * Greedy one-to-one assignment, batched.  Partition p holds n_base[p] x n_comp[p] distances, row-major (base-major),
+ * partitions back to back; 0xFFFFFFFF = the pair may not match.  Repeat per partition: among the pairs (i, j) with i and
+ * j both unmatched and dist < 0xFFFFFFFF take the smallest under the order (dist, i, j); match them; stop when none is
+ * left — i.e. the scan of the eligible pairs sorted by (dist, i, j).  Greedy, not optimal: [[1, 2], [2, 100]] gives
+ * (0, 0) and (1, 1).
+ * match_base / match_comp: per member, partitions back to back, the partner's index inside its partition or 0xFFFFFFFF.
+ * All pointers are HOST pointers; the call runs on the context's stream and returns with the outputs written.
+ * n_parts == 0 and partitions with n_base == 0 or n_comp == 0 are valid (their members stay unmatched).  SVX_E_INVALID
+ * for a null pointer where the counts call for data, SVX_E_TOO_LARGE for a partition of more than 2^20 pairs (nothing
+ * launched, the context stays usable).
+ * Partitions of fewer than `group_min` pairs (svx_ctx_set_match_group_min) run one LANE each, on the matrix where the
+ * call staged it and with the outputs as their only state; larger ones one WORKGROUP each: the matrix in LDS up to
+ * SVX_MATCH_LDS_PAIRS pairs (in the context's scratch beyond), a cached minimum per row, and per round a min-reduction
+ * over the rows and a rescan of only the rows whose cached column was just taken.  The outputs are identical on both.
+ */
+int svx_match_greedy_batch(svx_ctx* ctx, const uint32_t* dist, const uint32_t* n_base, const uint32_t* n_comp,
+                           uint32_t n_parts, uint32_t* match_base, uint32_t* match_comp);
+#define SVX_MATCH_LDS_PAIRS 32768
+/* Fewest pairs of a partition that takes the workgroup-per-partition kernel.  0 restores the default (9: 3 x 3 is the
+ * smallest size measured from which the group kernel is the faster one); 0xFFFFFFFF sends every
+ * partition down the lane path. */
+int svx_ctx_set_match_group_min(svx_ctx* ctx, uint32_t pairs);
+
+/*
  * Interval containment, batched: does ONE interval of list l contain query window q, for every (l, q)?
  * A key is contig << 32 | position.  List l owns the entries list_off[l] .. list_off[l+1] of start_key / end_key
  * (list_off[0] = 0, n_lists + 1 offsets), with start_key non-decreasing inside the list; the end keys are in no order.

@@ -102,6 +102,15 @@ class RecipeIn(C.Structure):
                 ("extra_at", C.c_uint64), ("seq_split", C.c_int64), ("mid_off", C.c_void_p), ("mid_len", C.c_void_p)]
 
 
+class VcfinColumns(C.Structure):
+    """svx_vcfin_columns (include/svx_vcfin.h)."""
+    _fields_ = [("n", C.c_uint64), ("type", C.c_void_p), ("contig", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p),
+                ("gt", C.c_void_p), ("seq_off", C.c_void_p), ("seq_len", C.c_void_p), ("seqs", C.c_void_p),
+                ("seq_bytes", C.c_uint64), ("line_off", C.c_void_p), ("line_len", C.c_void_p), ("line_no", C.c_void_p),
+                ("id_off", C.c_void_p), ("id_len", C.c_void_p), ("text", C.c_void_p), ("text_bytes", C.c_uint64),
+                ("header_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("counts", C.c_uint64 * 8)]
+
+
 class CollectOut(C.Structure):
     """svx_collect_out (include/svx.h)."""
     _fields_ = [("sig", SigSoa), ("sig_cap", C.c_uint64), ("n_sig", C.c_uint64), ("raw", C.c_void_p),
@@ -115,6 +124,10 @@ PIECE_UPPER, PIECE_REVCOMP = 1, 2
 LINKAGE_GROUP_LDS_N = 128        # SVX_LINKAGE_GROUP_LDS_N: largest partition whose working matrix the group kernel keeps in LDS
 COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
+MATCH_LDS_PAIRS = 32768          # SVX_MATCH_LDS_PAIRS: largest matrix the matching group kernel keeps in LDS
+MATCH_LANES_ONLY = 0xFFFFFFFF    # set_match_group_min: every partition down the lane path
+MATCH_NONE = 0xFFFFFFFF          # match_greedy_batch: "may not match" in dist, "unmatched" in the outputs
+MATCH_MAX_PAIRS = 1 << 20        # largest partition match_greedy_batch takes
 RAW_DTYPE = np.dtype([("kind", "<i4"), ("a0", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("a3", "<i4"),
                       ("a4", "<i4"), ("a5", "<i4"), ("pad", "<i4")])
 
@@ -142,6 +155,7 @@ SYMBOLS = {
     "svx_ctx_set_edit_wavefront_cap": (C.c_int, [_P, C.c_uint32]),
     "svx_ctx_set_pair_wait_free": (C.c_int, [_P, C.c_int]),
     "svx_ctx_set_linkage_group_min": (C.c_int, [_P, C.c_uint32]),
+    "svx_ctx_set_match_group_min": (C.c_int, [_P, C.c_uint32]),
     "svx_ctx_pair_retries": (C.c_int, [_P]),
     "svx_dev_malloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "svx_dev_free": (C.c_int, [_P, _P]),
@@ -181,6 +195,7 @@ SYMBOLS = {
     "svx_haplotype_distance_batch_mixed": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P]),
     "svx_pair_recipes": (C.c_int, [C.POINTER(RecipeIn), _P, _P, _P]),
     "svx_linkage_cut_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_double, _P]),
+    "svx_match_greedy_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
     "svx_cover_query": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "svx_cover_single": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     # native BAM ingest (include/svx_bam.h)
@@ -210,6 +225,10 @@ SYMBOLS = {
     "svx_sam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_paf_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_paf_set_query": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    # the VCF reader (include/svx_vcfin.h)
+    "svx_vcfin_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_char_p, C.c_int, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "svx_vcfin_get_columns": (C.c_int, [_P, C.POINTER(VcfinColumns)]),
+    "svx_vcfin_close": (None, [_P]),
     # the CIGAR-text parsers (include/svx_sam.h)
     "svx_cigar_text_parse": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_int]),
     "svx_cigar_text_parse_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
@@ -369,6 +388,11 @@ class Context:
         """Smallest partition linkage_cut_batch clusters with one workgroup instead of one lane (0: the default;
         LINKAGE_LANES_ONLY: none)."""
         self._check(self.lib.svx_ctx_set_linkage_group_min(self.h, int(n)))
+
+    def set_match_group_min(self, pairs):
+        """Fewest pairs of a partition match_greedy_batch assigns with one workgroup instead of one lane (0: the
+        default; MATCH_LANES_ONLY: none)."""
+        self._check(self.lib.svx_ctx_set_match_group_min(self.h, int(pairs)))
 
     # ---------------------------------------------------------------- device buffers
     def dev_array(self, host=None, nbytes=None):
@@ -743,6 +767,24 @@ class Context:
             self._check(self.lib.svx_linkage_cut_batch(self.h, _ptr(dist), _ptr(n_members), len(n_members),
                                                        float(cutoff), _ptr(labels)))
         return labels
+
+    def match_greedy_batch(self, dist, n_base, n_comp):
+        """Greedy one-to-one assignment for many partitions at once: partition p holds an n_base[p] x n_comp[p] matrix
+        of uint32 distances, row-major, back to back in `dist`; MATCH_NONE marks a pair that may not match.  Per
+        partition the eligible pairs are scanned in (dist, i, j) order and a pair is matched when both members are
+        free.  Returns (match_base, match_comp): per member, partitions back to back, the partner's index inside its
+        partition or MATCH_NONE (svx_match_greedy_batch)."""
+        dist = _as(dist, np.uint32).ravel()
+        n_base = _as(n_base, np.uint32)
+        n_comp = _as(n_comp, np.uint32)
+        if len(n_base) != len(n_comp) or int((n_base.astype(np.int64) * n_comp.astype(np.int64)).sum()) != len(dist):
+            raise SvxError(SVX_E_INVALID, "one n_comp per n_base, and dist as long as the partitions' matrices")
+        match_base = np.full(int(n_base.astype(np.int64).sum()), MATCH_NONE, np.uint32)
+        match_comp = np.full(int(n_comp.astype(np.int64).sum()), MATCH_NONE, np.uint32)
+        if len(n_base):
+            self._check(self.lib.svx_match_greedy_batch(self.h, _ptr(dist), _ptr(n_base), _ptr(n_comp), len(n_base),
+                                                        _ptr(match_base), _ptr(match_comp)))
+        return match_base, match_comp
 
     def cover_query(self, start_key, end_key, list_off, q_lo, q_hi):
         """For every list l and query q: does ONE interval of the list contain the window [q_lo[q], q_hi[q]]?

@@ -44,6 +44,7 @@ struct svx_ctx {
     uint64_t small_batch_ops = 1ull << 23;  // svx_ctx_set_small_batch_ops: largest batch of the two-launch CIGAR path
     bool split_chain = false;               // svx_ctx_set_split_chain: the split-segment chain as three launches
     uint32_t link_group_min = 0;            // svx_ctx_set_linkage_group_min: smallest partition of the group kernel (0: default)
+    uint32_t match_group_min = 0;           // svx_ctx_set_match_group_min: fewest pairs of the matching group kernel (0: default)
     char err[512] = {0};
 };
 
