@@ -760,6 +760,53 @@ int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end
                     uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out);
 
 /*
+ * svx_cover_query's question answered with WHICH interval: inputs, layout and refusals are those of svx_cover_query (one
+ * checker serves both), the output is a word per (list, query):
+ *     out[l * n_q + q] = the index inside list l of the covering entry, SVX_COVER_NONE when none covers.
+ * Of the list's entries with start_key <= q_lo[q] the one with the largest end key is taken, the lowest index among
+ * equal end keys; it is the answer when its end key is >= q_hi[q].  So out != SVX_COVER_NONE exactly where
+ * svx_cover_query answers 1.  SVX_E_TOO_LARGE for a list of 2^32 - 1 entries or more.
+ * Two launches, as svx_cover_query's: the prefix maximum runs as a prefix arg-max over (end key, index) pairs.
+ */
+#define SVX_COVER_NONE 0xFFFFFFFFu
+int svx_cover_locate(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                     uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint32_t* out);
+
+/*
+ * Lift-over through the CIGAR, batched: where does reference position q_ref[q] lie on the query sequence (SEQ) of
+ * alignment q_aln[q]?  `cigar` holds the BAM-native words (len << 4 | op) of n_aln alignments back to back, alignment a
+ * owning aln_off[a] .. aln_off[a+1] (aln_off[0] = 0) and starting at reference position ref_start[a].  With r = q_ref[q],
+ * walking the ops of the alignment with a reference cursor (M D N = X advance it) and a query cursor that counts SEQ
+ * bases (M I S = X advance it; H, P and op codes above 8 advance nothing):
+ *     SVX_LIFT_ALIGNED   r lies inside an M / = / X op: out_query = the query offset of the base aligned to r
+ *     SVX_LIFT_DELETED   r lies inside a D / N op: out_query = the query offset of the next base behind the op
+ *     SVX_LIFT_END       r is the first reference position behind the alignment: out_query = the query offset behind the
+ *                        last reference-consuming op (trailing I / S are not counted)
+ *     SVX_LIFT_OUTSIDE   anything else (also every position of an alignment without reference-consuming ops): out_query = 0
+ * Bases inserted immediately in front of the op that covers r lie to the left of the lifted point.
+ * All pointers are HOST pointers (svx_cigar_lift_dev: `d_cigar` is a pool of n_ops words in HBM, complete — a reader's
+ * device pool after its wait —, the rest host pointers); the call returns with both outputs written.  SVX_E_INVALID,
+ * nothing launched and the context usable, for aln_off[0] != 0, decreasing offsets, q_aln[q] >= n_aln and (dev)
+ * aln_off[n_aln] > n_ops; SVX_E_NOMEM when the workspace cannot be had.  n_q == 0, n_aln == 0 and alignments without
+ * ops are valid.
+ * Four launches, nothing handed between workgroups inside one: the (reference, query) consumption of every op summed per
+ * chunk of SVX_LIFT_CHUNK ops; one workgroup's exclusive scan of the chunk sums, SVX_LIFT_CHUNK of them per pass with a
+ * carry; the inclusive 64-bit prefixes of both per op into the context workspace (a pool's reference consumption exceeds
+ * 2^32); one lane per query: the upper bound of r - ref_start + prefix(first op - 1) among its alignment's reference
+ * prefixes.  With n_q == 0 nothing is looked at.
+ */
+#define SVX_LIFT_OUTSIDE 0
+#define SVX_LIFT_ALIGNED 1
+#define SVX_LIFT_DELETED 2
+#define SVX_LIFT_END 3
+#define SVX_LIFT_CHUNK 1024
+int svx_cigar_lift(svx_ctx* ctx, const uint32_t* cigar, const uint64_t* aln_off, const int32_t* ref_start, uint32_t n_aln,
+                   const uint32_t* q_aln, const int64_t* q_ref, uint32_t n_q, uint32_t* out_query, uint8_t* out_state);
+int svx_cigar_lift_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, const uint64_t* aln_off, const int32_t* ref_start,
+                       uint32_t n_aln, const uint32_t* q_aln, const int64_t* q_ref, uint32_t n_q, uint32_t* out_query,
+                       uint8_t* out_state);
+
+/*
  * Single coverage, batched: where does EXACTLY one entry of list l lie over the reference?  The lists are laid out as
  * for svx_cover_query; an entry is the half-open key range [start_key, end_key).  With depth(p) the number of entries
  * of the list with start <= p < end, the list's segments are the maximal ranges [a, b) on which depth is 1 and the one

@@ -83,6 +83,10 @@ typedef struct svx_vcfin_columns {
  * message. */
 int svx_vcfin_open(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
                    int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap);
+/* The same file as a list of SITES: the sample columns are not looked at, so no record is SVX_VCFIN_NOT_CARRIED and gt is
+ * 0 in every row — a record whose genotype is 0/0 or ./. in every sample is a site like any other. */
+int svx_vcfin_open_sites(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, int passonly,
+                         int n_threads, svx_vcfin** out, char* err, size_t err_cap);
 int svx_vcfin_get_columns(const svx_vcfin* v, svx_vcfin_columns* out);
 void svx_vcfin_close(svx_vcfin* v);
 

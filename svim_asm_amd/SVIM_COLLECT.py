@@ -295,9 +295,14 @@ def _coverage_of(s, ctx):
     supplementary ones included), as int64 columns ordered by (tid, start) with ties in loop order: what
     --keep_coverage persists (SVIM_MERGE.keep_coverage).  end = pos + ref_len of svx_cigar_stats, from the reader's own
     copy of the CIGAR pool in HBM where there is one; a record without reference bases gives no interval."""
+    return _coverage_records_of(s, ctx)[:3]
+
+
+def _coverage_records_of(s, ctx):
+    """_coverage_of with a fourth column: the record (index into s.rec's columns) every interval comes from."""
     r = s.rec
     if len(s.order) == 0:
-        return tuple(np.zeros(0, np.int64) for _ in range(3))
+        return tuple(np.zeros(0, np.int64) for _ in range(4))
     base = getattr(r, "base", None)
     pool = base.device_pool(wait=True) if base is not None and hasattr(base, "device_pool") and r.cigar is base._cigar else None
     if pool is not None:
@@ -308,12 +313,12 @@ def _coverage_of(s, ctx):
     tid = np.asarray(r.tid, dtype=np.int64)[s.order]
     start = np.asarray(r.pos, dtype=np.int64)[s.order]
     has = ref_len > 0
-    tid, start, end = tid[has], start[has], (start + ref_len)[has]
+    tid, start, end, rec = tid[has], start[has], (start + ref_len)[has], np.asarray(s.order, dtype=np.int64)[has]
     key = (tid << 32) | start
     if len(key) > 1 and bool((key[1:] < key[:-1]).any()):  # (a view that ranks its contigs otherwise, an unsorted source)
         o = np.argsort(key, kind="stable")
-        tid, start, end = tid[o], start[o], end[o]
-    return tid, start, end
+        tid, start, end, rec = tid[o], start[o], end[o], rec[o]
+    return tid, start, end, rec
 
 
 def _submit(samples, options, ctx):

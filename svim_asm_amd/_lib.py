@@ -122,6 +122,9 @@ SEG_DTYPE = np.dtype([("q_start", "<i4"), ("q_end", "<i4"), ("ref_id", "<i4"), (
 HAP_PIECE_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("repeat", "<u2"), ("flags", "<u2")])  # svx_hap_piece
 PIECE_UPPER, PIECE_REVCOMP = 1, 2
 LINKAGE_GROUP_LDS_N = 128        # SVX_LINKAGE_GROUP_LDS_N: largest partition whose working matrix the group kernel keeps in LDS
+COVER_NONE = 0xFFFFFFFF          # SVX_COVER_NONE: cover_locate's "no entry covers"
+LIFT_OUTSIDE, LIFT_ALIGNED, LIFT_DELETED, LIFT_END = range(4)  # SVX_LIFT_*: cigar_lift's states
+LIFT_CHUNK = 1024                # SVX_LIFT_CHUNK: ops per workgroup of cigar_lift's scan, chunk sums per pass of its second level
 COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 MATCH_LDS_PAIRS = 32768          # SVX_MATCH_LDS_PAIRS: largest matrix the matching group kernel keeps in LDS
@@ -198,6 +201,9 @@ SYMBOLS = {
     "svx_match_greedy_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P]),
     "svx_cover_query": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "svx_cover_single": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    "svx_cover_locate": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
+    "svx_cigar_lift": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
+    "svx_cigar_lift_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -227,6 +233,7 @@ SYMBOLS = {
     "svx_paf_set_query": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     # the VCF reader (include/svx_vcfin.h)
     "svx_vcfin_open": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_char_p, C.c_int, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "svx_vcfin_open_sites": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_int, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_vcfin_get_columns": (C.c_int, [_P, C.POINTER(VcfinColumns)]),
     "svx_vcfin_close": (None, [_P]),
     # the CIGAR-text parsers (include/svx_sam.h)
@@ -805,6 +812,56 @@ class Context:
             self._check(self.lib.svx_cover_query(self.h, _ptr(start_key), _ptr(end_key), _ptr(list_off), n_lists,
                                                  _ptr(q_lo), _ptr(q_hi), n_q, _ptr(out)))
         return out
+
+    def cover_locate(self, start_key, end_key, list_off, q_lo, q_hi):
+        """cover_query answered with WHICH interval: uint32 [n_lists, n_q], the index inside list l of the entry that
+        contains the window — of the entries with start_key <= q_lo the one with the largest end key, the lowest index
+        among equal end keys —, COVER_NONE where cover_query answers 0 (svx_cover_locate)."""
+        start_key = _as(start_key, np.uint64)
+        end_key = _as(end_key, np.uint64)
+        list_off = _as(list_off, np.uint64)
+        q_lo = _as(q_lo, np.uint64)
+        q_hi = _as(q_hi, np.uint64)
+        if len(list_off) < 1 or len(start_key) != len(end_key) or len(q_lo) != len(q_hi) or \
+                int(list_off[-1]) != len(start_key):
+            raise SvxError(SVX_E_INVALID, "n_lists + 1 offsets ending at the number of intervals, one end per start, "
+                                          "one hi per lo")
+        n_lists, n_q = len(list_off) - 1, len(q_lo)
+        out = np.full((n_lists, n_q), COVER_NONE, np.uint32)
+        if n_lists and n_q:
+            self._check(self.lib.svx_cover_locate(self.h, _ptr(start_key), _ptr(end_key), _ptr(list_off), n_lists,
+                                                  _ptr(q_lo), _ptr(q_hi), n_q, _ptr(out)))
+        return out
+
+    def cigar_lift(self, cigar, aln_off, ref_start, q_aln, q_ref, n_ops=None):
+        """Where reference position q_ref[q] lies on the query sequence of alignment q_aln[q], through the CIGAR:
+        (uint32 query offsets, uint8 states LIFT_*), see svx_cigar_lift in include/svx.h.  `cigar`: packed u32 words of
+        all alignments, alignment a owning aln_off[a]:aln_off[a + 1] — or, with `n_ops`, the device address of a pool of
+        n_ops words that is in HBM already (a reader's device_pool after its wait: svx_cigar_lift_dev)."""
+        aln_off = _as(aln_off, np.uint64)
+        ref_start = _as(ref_start, np.int32)
+        q_aln = _as(q_aln, np.uint32)
+        q_ref = _as(q_ref, np.int64)
+        n_aln = len(aln_off) - 1 if len(aln_off) else 0
+        if len(ref_start) != n_aln or len(q_aln) != len(q_ref):
+            raise SvxError(SVX_E_INVALID, "one ref_start per alignment, one q_ref per q_aln")
+        n_q = len(q_aln)
+        query, state = np.zeros(n_q, np.uint32), np.zeros(n_q, np.uint8)
+        if n_q == 0:
+            return query, state
+        if n_aln == 0:
+            raise SvxError(SVX_E_INVALID, "queries without alignments")
+        if n_ops is None:
+            cigar = _as(cigar, np.uint32)
+            if len(cigar) < int(aln_off[-1]):
+                raise SvxError(SVX_E_INVALID, "cigar shorter than aln_off[-1]")
+            rc = self.lib.svx_cigar_lift(self.h, _ptr(cigar), _ptr(aln_off), _ptr(ref_start), n_aln, _ptr(q_aln), _ptr(q_ref),
+                                         n_q, _ptr(query), _ptr(state))
+        else:
+            rc = self.lib.svx_cigar_lift_dev(self.h, cigar, int(n_ops), _ptr(aln_off), _ptr(ref_start), n_aln, _ptr(q_aln),
+                                             _ptr(q_ref), n_q, _ptr(query), _ptr(state))
+        self._check(rc)
+        return query, state
 
     def cover_single(self, start_key, end_key, list_off):
         """The ranges on which exactly ONE entry of a list — and the same one throughout — lies over the reference, per

@@ -18,6 +18,10 @@
 // Every word of the prefix maxima is written by the scan before the search reads it, and only inside the lists'
 // ranges: nothing depends on what the workspace held (the scratch contract, include/svx.h).
 //
+// svx_cover_locate answers the same batch with WHICH entry covers: k_locate_scan is k_cover_scan over
+// (end key, list-local index) pairs under arg-max — the lowest index among equal keys —, k_locate_search writes the index
+// in front of the upper bound where its key reaches hi, SVX_COVER_NONE elsewhere.
+//
 // svx_cover_single asks of the same lists where EXACTLY one entry lies over the reference: the maximal
 // ranges on which one entry, and the same one, is the only one with start <= p < end.  With the entries in start order
 // slot k is [s_k, s_k+1) (the last one open to the right); only entries 0..k can be active inside it, so with
@@ -31,38 +35,19 @@
 //   k_single_pack     every list's segments to their final contiguous place.
 // A list's pack reads the `count` words its scan wrote and nothing else.
 #include "svx_internal.h"
+#include "svx_scan_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kScanThreads;
 constexpr int kPer = SVX_COVER_SCAN_CHUNK / kThreads;  // consecutive elements of one thread
-constexpr int kWaves = kThreads / 64;
+constexpr int kWaves = kScanWaves;
 static_assert(kPer * kThreads == SVX_COVER_SCAN_CHUNK && kPer == 4, "four elements per thread, loaded as two 16-byte words");
 constexpr uint32_t kMaxGridY = 65535;
 
-// DPP lane movement (gfx9 family): 0 flows into lanes without a source — the identity of max over unsigned keys, of
-// the sum, and (as a pair) of the top two
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xF, false);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ uint64_t max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 // the two largest end keys of a set of entries, m1 >= m2; (0, 0): no entry
 struct Top2 {
     uint64_t m1, m2;
-};
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint64_t dpp0(uint64_t v) { return dpp0_64<CTRL, ROW_MASK>(v); }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ Top2 dpp0(Top2 v) { return Top2{dpp0_64<CTRL, ROW_MASK>(v.m1), dpp0_64<CTRL, ROW_MASK>(v.m2)}; }
-struct OpMax {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return max64(a, b); }
-};
-struct OpAdd {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
 };
 // top two of the four: an element folded in twice would read as depth 2 — disjoint operands only
 struct OpTop2 {
@@ -70,19 +55,17 @@ struct OpTop2 {
         return Top2{max64(a.m1, b.m1), max64(min64(a.m1, b.m1), max64(a.m2, b.m2))};
     }
 };
-// inclusive scan over the lanes 0..l of the wave; 0 is op's identity.  Every step combines two DISJOINT lane ranges
-// (row_shr:n the n lanes in front of the 2^k a lane holds, row_bcast the whole rows in front), rows a step's mask leaves
-// out and lanes without a source combine with 0: op need not be idempotent.
-template <typename T, typename Op>
-__device__ __forceinline__ T wave_scan(T v, Op op) {
-    v = op(v, dpp0<0x111, 0xF>(v));  // row_shr:1
-    v = op(v, dpp0<0x112, 0xF>(v));  // row_shr:2
-    v = op(v, dpp0<0x114, 0xF>(v));  // row_shr:4
-    v = op(v, dpp0<0x118, 0xF>(v));  // row_shr:8
-    v = op(v, dpp0<0x142, 0xA>(v));  // row_bcast:15 into rows 1 and 3
-    v = op(v, dpp0<0x143, 0xC>(v));  // row_bcast:31 into rows 2 and 3
-    return v;
-}
+// the largest end key of a set of entries and the list-local index of the entry that holds it, the lowest index among
+// equal keys; (0, 0): no entry — entry 0 is in every non-empty prefix, so a maximum of 0 is held by index 0 at the latest
+struct ArgMax {
+    uint64_t key;
+    uint32_t idx, pad;
+};
+struct OpArgMax {
+    __device__ __forceinline__ ArgMax operator()(ArgMax a, ArgMax b) const {
+        return (a.key > b.key || (a.key == b.key && a.idx <= b.idx)) ? a : b;
+    }
+};
 // inclusive maximum over the lanes 0..l of the wave
 __device__ __forceinline__ uint64_t wave_scan_max(uint64_t v) { return wave_scan(v, OpMax()); }
 
@@ -140,23 +123,64 @@ __global__ __launch_bounds__(kThreads) void k_cover_search(const uint64_t* __res
     }
 }
 
-// Exclusive prefix of a lane's inclusive wave scan `incl` over the whole workgroup: the lanes in front of it in its wave
-// (wave_shr:1, lane 0 receives 0), the waves in front through `s_w`, and `total` of all four waves.  One barrier; the
-// caller keeps a second one between two uses of the same `s_w`.
-template <typename T, typename Op>
-__device__ __forceinline__ T group_before(T incl, T* s_w, int tid, Op op, T* total) {
-    const int wave = tid >> 6;
-    if ((tid & 63) == 63) s_w[wave] = incl;
-    T before = dpp0<0x138, 0xF>(incl);
-    __syncthreads();
-    T all = s_w[0];
+// svx_cover_locate: k_cover_scan as a prefix ARG-max — the same passes, the same fold of the waves through LDS, the same
+// carry, over (end key, list-local index) pairs; amax / aidx[i]: the pair of the list's entries up to i
+__global__ __launch_bounds__(kThreads) void k_locate_scan(const uint64_t* __restrict__ end_key, const uint64_t* __restrict__ list_off,
+                                                          uint64_t* __restrict__ amax, uint32_t* __restrict__ aidx) {
+    __shared__ ArgMax s_wave[2][kWaves];
+    const uint64_t lo = list_off[blockIdx.x], hi = list_off[blockIdx.x + 1];
+    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const OpArgMax op;
+    ArgMax carry = ArgMax{0, 0, 0};
+    int slot = 0;
+    // (the trip count depends on the list alone: every lane of the group takes every pass, DPP and barrier included)
+    for (uint64_t base = lo; base < hi; base += SVX_COVER_SCAN_CHUNK, slot ^= 1) {
+        const uint64_t first = base + (uint64_t)tid * kPer;
+        ArgMax v[kPer];
 #pragma unroll
-    for (int w = 1; w < kWaves; ++w) {
-        if (w == wave) before = op(before, all);  // (waves 0..w-1, disjoint from this wave's lanes)
-        all = op(all, s_w[w]);
+        for (int j = 0; j < kPer; ++j) v[j] = first + j < hi ? ArgMax{end_key[first + j], (uint32_t)(first + j - lo), 0} : ArgMax{0, 0, 0};
+#pragma unroll
+        for (int j = 1; j < kPer; ++j) v[j] = op(v[j - 1], v[j]);
+        const ArgMax incl = wave_scan(v[kPer - 1], op);
+        if ((tid & 63) == 63) s_wave[slot][wave] = incl;
+        ArgMax before = dpp0<0x138, 0xF>(incl);  // wave_shr:1, lane 0 receives (0, 0)
+        __syncthreads();  // (two buffers in turn, as in k_cover_scan)
+        ArgMax total = ArgMax{0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const ArgMax t = s_wave[slot][w];
+            if (w < wave) before = op(before, t);
+            total = op(total, t);
+        }
+        before = op(before, carry);
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (first + j < hi) {
+                const ArgMax m = op(before, v[j]);
+                amax[first + j] = m.key;
+                aidx[first + j] = m.idx;
+            }
+        carry = op(carry, total);
     }
-    *total = all;
-    return before;
+}
+
+__global__ __launch_bounds__(kThreads) void k_locate_search(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ amax,
+                                                            const uint32_t* __restrict__ aidx, const uint64_t* __restrict__ list_off,
+                                                            uint32_t n_lists, const uint64_t* __restrict__ q_lo,
+                                                            const uint64_t* __restrict__ q_hi, uint32_t n_q, uint32_t* __restrict__ out) {
+    const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
+    if (q >= n_q) return;
+    const uint64_t lo = q_lo[q], hi = q_hi[q];
+    for (uint32_t l = blockIdx.y; l < n_lists; l += gridDim.y) {
+        const uint64_t b = list_off[l], e = list_off[l + 1];
+        // first element with start_key > lo
+        uint64_t a = b, n = e - b;
+        while (n) {
+            const uint64_t half = n >> 1;
+            if (start_key[a + half] <= lo) { a += half + 1; n -= half + 1; } else n = half;
+        }
+        out[(size_t)l * n_q + q] = (a > b && amax[a - 1] >= hi) ? aidx[a - 1] : SVX_COVER_NONE;
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_single_scan(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ end_key,
@@ -282,26 +306,35 @@ int check_lists(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
     return SVX_OK;
 }
 
+// What svx_cover_query and svx_cover_locate require of a batch (n_lists and n_q above 0): check_lists, and every query
+// on one contig with lo <= hi.
+int check_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, const void* out) {
+    if (!list_off || !q_lo || !q_hi || !out) return SVX_E_INVALID;
+    const int rc = check_lists(ctx, who, start_key, end_key, list_off, n_lists, false);
+    if (rc != SVX_OK) return rc;
+    for (uint32_t q = 0; q < n_q; ++q) {
+        if ((q_lo[q] >> 32) != (q_hi[q] >> 32)) {
+            SVX_SET_ERR(ctx, "%s: query %u starts and ends on different contigs", who, q);
+            return SVX_E_INVALID;
+        }
+        if (q_lo[q] > q_hi[q]) {
+            SVX_SET_ERR(ctx, "%s: query %u has lo > hi", who, q);
+            return SVX_E_INVALID;
+        }
+    }
+    return SVX_OK;
+}
+
 }  // namespace
 
 extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
                                uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out) {
     if (!ctx) return SVX_E_INVALID;
     if (n_lists == 0 || n_q == 0) return SVX_OK;
-    if (!list_off || !q_lo || !q_hi || !out) return SVX_E_INVALID;
-    int rc = check_lists(ctx, "svx_cover_query", start_key, end_key, list_off, n_lists, false);
+    int rc = check_batch(ctx, "svx_cover_query", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
     if (rc != SVX_OK) return rc;
     const uint64_t n = list_off[n_lists];
-    for (uint32_t q = 0; q < n_q; ++q) {
-        if ((q_lo[q] >> 32) != (q_hi[q] >> 32)) {
-            SVX_SET_ERR(ctx, "svx_cover_query: query %u starts and ends on different contigs", q);
-            return SVX_E_INVALID;
-        }
-        if (q_lo[q] > q_hi[q]) {
-            SVX_SET_ERR(ctx, "svx_cover_query: query %u has lo > hi", q);
-            return SVX_E_INVALID;
-        }
-    }
     const size_t n_out = (size_t)n_lists * n_q;
     if (n == 0) {  // empty lists only
         memset(out, 0, n_out);
@@ -339,6 +372,61 @@ extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const ui
     rc = svx_timing_end(ctx);
     if (rc != SVX_OK) return rc;
     SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SVX_OK;
+}
+
+extern "C" int svx_cover_locate(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                                uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint32_t* out) {
+    if (!ctx) return SVX_E_INVALID;
+    if (n_lists == 0 || n_q == 0) return SVX_OK;
+    int rc = check_batch(ctx, "svx_cover_locate", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
+    if (rc != SVX_OK) return rc;
+    const uint64_t n = list_off[n_lists];
+    for (uint32_t l = 0; l < n_lists; ++l)
+        if (list_off[l + 1] - list_off[l] >= SVX_COVER_NONE) {  // (an index has to differ from "none")
+            SVX_SET_ERR(ctx, "svx_cover_locate: list %u has %llu entries", l, (unsigned long long)(list_off[l + 1] - list_off[l]));
+            return SVX_E_TOO_LARGE;
+        }
+    const size_t n_out = (size_t)n_lists * n_q;
+    if (n == 0) {  // empty lists only
+        memset(out, 0xFF, n_out * 4);
+        return SVX_OK;
+    }
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    rc = svx_stage_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8) + 2 * svx_take_bytes(n_q, 8) +
+                                        svx_take_bytes(n_out, 4));
+    if (rc != SVX_OK) return rc;
+    rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8) + svx_take_bytes(n, 4));
+    if (rc != SVX_OK) return rc;
+    uint64_t* d_start = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_end = svx_stage_take<uint64_t>(ctx, n);
+    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    uint64_t* d_lo = svx_stage_take<uint64_t>(ctx, n_q);
+    uint64_t* d_hi = svx_stage_take<uint64_t>(ctx, n_q);
+    uint32_t* d_out = svx_stage_take<uint32_t>(ctx, n_out);
+    uint64_t* d_amax = svx_ws_take<uint64_t>(ctx, n);
+    uint32_t* d_aidx = svx_ws_take<uint32_t>(ctx, n);
+    SVX_HIP(ctx, hipMemcpyAsync(d_start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_lo, q_lo, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d_hi, q_hi, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = svx_timing_begin(ctx);
+    if (rc != SVX_OK) return rc;
+    hipLaunchKernelGGL(k_locate_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d_end, d_off, d_amax, d_aidx);
+    SVX_HIP(ctx, hipGetLastError());
+    rc = svx_timing_mark(ctx, 1);
+    if (rc != SVX_OK) return rc;
+    const dim3 grid((n_q + kThreads - 1) / kThreads, n_lists < kMaxGridY ? n_lists : kMaxGridY);
+    hipLaunchKernelGGL(k_locate_search, grid, dim3(kThreads), 0, ctx->stream, d_start, d_amax, d_aidx, d_off, n_lists, d_lo, d_hi, n_q,
+                       d_out);
+    SVX_HIP(ctx, hipGetLastError());
+    rc = svx_timing_mark(ctx, 2);
+    if (rc != SVX_OK) return rc;
+    rc = svx_timing_end(ctx);
+    if (rc != SVX_OK) return rc;
+    SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }

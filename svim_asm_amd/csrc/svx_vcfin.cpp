@@ -282,8 +282,9 @@ int inflate_bgzf(svx_vcfin* v, const char* path, int n_threads, std::string* err
 
 }  // namespace
 
-extern "C" int svx_vcfin_open(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
-                              int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
+// svx_vcfin_open, or with `sites` svx_vcfin_open_sites: the sample columns are not looked at
+static int open_vcf(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample, bool sites,
+                    int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
     svx_vcfin* v = nullptr;
     auto refuse = [&](int rc, const std::string& msg) {
         delete v;
@@ -346,8 +347,8 @@ extern "C" int svx_vcfin_open(const char* path, int32_t n_ref, const char* const
             cols.emplace_back(map + c, fe - c);
             c = fe + 1;
         }
-        if (cols.size() > 9) sample_col = 9;
-        if (sample) {
+        if (cols.size() > 9 && !sites) sample_col = 9;
+        if (sample && !sites) {
             sample_col = -1;
             for (size_t k = 9; k < cols.size(); ++k)
                 if (cols[k] == sample) { sample_col = (int)k; break; }
@@ -385,6 +386,16 @@ extern "C" int svx_vcfin_open(const char* path, int32_t n_ref, const char* const
     }
     *out = v;
     return SVX_OK;
+}
+
+extern "C" int svx_vcfin_open(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
+                              int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
+    return open_vcf(path, n_ref, names, lengths, sample, false, passonly, n_threads, out, err, err_cap);
+}
+
+extern "C" int svx_vcfin_open_sites(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, int passonly,
+                                    int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
+    return open_vcf(path, n_ref, names, lengths, nullptr, true, passonly, n_threads, out, err, err_cap);
 }
 
 extern "C" int svx_vcfin_get_columns(const svx_vcfin* v, svx_vcfin_columns* out) {

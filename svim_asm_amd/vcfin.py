@@ -41,14 +41,28 @@ def _column(ptr, n, dtype):
 def read_vcf(path, contigs, contig_len, sample=None, passonly=False, threads=0):
     """Read `path` (plain text or BGZF) against the contig dictionary of the genome's .fai.  sample: the sample column
     by name (None: the first).  Raises VcfFormatError with the reader's message."""
+    return _read(path, contigs, contig_len, sample, passonly, threads, False)
+
+
+def read_sites(path, contigs, contig_len, passonly=False, threads=0):
+    """read_vcf for a list of SITES (svx_vcfin_open_sites): the sample columns are not looked at — no record is
+    not_carried, the table's gt is 0 throughout."""
+    return _read(path, contigs, contig_len, None, passonly, threads, True)
+
+
+def _read(path, contigs, contig_len, sample, passonly, threads, sites):
     lib = _lib.load()
     names = [c.encode() for c in contigs]
     name_arr = (C.c_char_p * len(names))(*names)
     lengths = np.ascontiguousarray(contig_len, dtype=np.int64)
     h, err = C.c_void_p(), C.create_string_buffer(1024)
-    rc = lib.svx_vcfin_open(str(path).encode(), len(names), C.cast(name_arr, C.c_void_p), lengths.ctypes.data,
-                            None if sample is None else str(sample).encode(), 1 if passonly else 0, int(threads), C.byref(h),
-                            err, len(err))
+    if sites:
+        rc = lib.svx_vcfin_open_sites(str(path).encode(), len(names), C.cast(name_arr, C.c_void_p), lengths.ctypes.data,
+                                      1 if passonly else 0, int(threads), C.byref(h), err, len(err))
+    else:
+        rc = lib.svx_vcfin_open(str(path).encode(), len(names), C.cast(name_arr, C.c_void_p), lengths.ctypes.data,
+                                None if sample is None else str(sample).encode(), 1 if passonly else 0, int(threads), C.byref(h),
+                                err, len(err))
     if rc != _lib.SVX_OK:
         raise VcfFormatError(err.value.decode("utf-8", "replace") or "svx_vcfin_open failed (%d)" % rc)
     try:
