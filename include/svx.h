@@ -827,6 +827,51 @@ int svx_cigar_lift_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, co
 int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
                      uint32_t n_lists, uint64_t* seg_lo, uint64_t* seg_hi, uint64_t* seg_off);
 
+/*
+ * Mismatching columns, batched: where do the aligned bases of alignment a differ from the reference?  `cigar`, `aln_off`
+ * and `ref_start` are svx_cigar_lift's.  `bases` is ONE pool of n_bases ASCII bytes in any case; alignment a's reference
+ * window — the reference bases [ref_start[a], ref_start[a] + ref_len[a]) — lies at bases[ref_off[a] ..], its SEQ in BAM
+ * orientation, soft clips included, at bases[qry_off[a] .. qry_off[a] + qry_len[a]).  The definition is this loop:
+ *     r = q = 0
+ *     for every op (code, len) of alignment a:
+ *         if code is M, = or X:
+ *             for j in 0 .. len - 1, if r + j < ref_len[a] and q + j < qry_len[a]:
+ *                 R = bases[ref_off[a] + r + j] & 0xDF;  Q = bases[qry_off[a] + q + j] & 0xDF
+ *                 if R and Q are both one of 'A' 'C' 'G' 'T' and R != Q:
+ *                     emit (a, ref_start[a] + r + j, q + j, R, Q)
+ *         if code is M D N = X: r += len          (svx_cigar_lift's cursors; note that svx_cigar_extract's
+ *         if code is M I S = X: q += len           reference cursor does NOT advance over N)
+ *         H, P and codes above 8 advance nothing
+ * A column outside either length emits nothing and none of its bytes is compared; a CIGAR that uses more bases than the
+ * lengths say is not an error.  Output (SoA, 14 B per event): aln, ref_pos, qry_pos (uint32), ref_base, qry_base (upper
+ * case), ascending by (alignment, ref_pos) and identical from run to run — positions are dealt out to lanes and the rows
+ * placed by prefix sums, no atomics.  `cap` / `n_out` as for svx_cigar_extract: *n_out always receives the exact count,
+ * min(count, cap) rows are written, SVX_E_CAPACITY beyond cap.
+ * All pointers are HOST pointers (svx_cigar_mismatch_dev: `d_cigar` is a pool of n_ops words in HBM, complete, as for
+ * svx_cigar_lift_dev); the call returns with the rows written.  SVX_E_INVALID — nothing launched, the context usable, the
+ * message names the alignment — for aln_off[0] != 0, decreasing offsets, a negative ref_start, ref_start + ref_len above
+ * 2^32 - 1, ref_off + ref_len or qry_off + qry_len above n_bases, and (dev) aln_off[n_aln] > n_ops.  n_aln == 0,
+ * alignments without ops and zero lengths are valid.  Limits: per-alignment query cursor sums < 2^32; fewer than 2^31 - 1
+ * tiles and chunks of ops (SVX_E_TOO_LARGE).
+ * Six launches: svx_cigar_lift's three for the 64-bit prefixes; one workgroup per tile of SVX_MISMATCH_TILE reference
+ * positions of one alignment's window, 16 positions per lane, counting; one workgroup's exclusive scan of the tile counts;
+ * the tile launch again, writing.
+ */
+#define SVX_MISMATCH_TILE 4096
+typedef struct svx_mismatch_soa {
+    uint32_t* aln;
+    uint32_t* ref_pos;
+    uint32_t* qry_pos;
+    uint8_t* ref_base;
+    uint8_t* qry_base;
+} svx_mismatch_soa;
+int svx_cigar_mismatch(svx_ctx* ctx, const uint32_t* cigar, const uint64_t* aln_off, const int32_t* ref_start, uint32_t n_aln,
+                       const uint8_t* bases, uint64_t n_bases, const uint64_t* ref_off, const uint32_t* ref_len,
+                       const uint64_t* qry_off, const uint32_t* qry_len, svx_mismatch_soa out, uint64_t cap, uint64_t* n_out);
+int svx_cigar_mismatch_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, const uint64_t* aln_off, const int32_t* ref_start,
+                           uint32_t n_aln, const uint8_t* bases, uint64_t n_bases, const uint64_t* ref_off, const uint32_t* ref_len,
+                           const uint64_t* qry_off, const uint32_t* qry_len, svx_mismatch_soa out, uint64_t cap, uint64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

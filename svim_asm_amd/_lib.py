@@ -41,6 +41,11 @@ class SigSoa(C.Structure):
                 ("len", C.c_void_p), ("type", C.c_void_p)]
 
 
+class MismatchSoa(C.Structure):
+    """svx_mismatch_soa (include/svx.h)."""
+    _fields_ = [("aln", C.c_void_p), ("ref_pos", C.c_void_p), ("qry_pos", C.c_void_p), ("ref_base", C.c_void_p), ("qry_base", C.c_void_p)]
+
+
 class AlnStats(C.Structure):
     _fields_ = [("ref_len", C.c_void_p), ("q_start", C.c_void_p), ("q_end", C.c_void_p),
                 ("read_len", C.c_void_p), ("n_hard", C.c_void_p)]
@@ -125,6 +130,7 @@ LINKAGE_GROUP_LDS_N = 128        # SVX_LINKAGE_GROUP_LDS_N: largest partition wh
 COVER_NONE = 0xFFFFFFFF          # SVX_COVER_NONE: cover_locate's "no entry covers"
 LIFT_OUTSIDE, LIFT_ALIGNED, LIFT_DELETED, LIFT_END = range(4)  # SVX_LIFT_*: cigar_lift's states
 LIFT_CHUNK = 1024                # SVX_LIFT_CHUNK: ops per workgroup of cigar_lift's scan, chunk sums per pass of its second level
+MISMATCH_TILE = 4096             # SVX_MISMATCH_TILE: reference positions of one alignment per workgroup of cigar_mismatch
 COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 MATCH_LDS_PAIRS = 32768          # SVX_MATCH_LDS_PAIRS: largest matrix the matching group kernel keeps in LDS
@@ -204,6 +210,10 @@ SYMBOLS = {
     "svx_cover_locate": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "svx_cigar_lift": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
     "svx_cigar_lift_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
+    "svx_cigar_mismatch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, MismatchSoa, C.c_uint64,
+                                     C.POINTER(C.c_uint64)]),
+    "svx_cigar_mismatch_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, MismatchSoa,
+                                         C.c_uint64, C.POINTER(C.c_uint64)]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -862,6 +872,47 @@ class Context:
                                              _ptr(q_ref), n_q, _ptr(query), _ptr(state))
         self._check(rc)
         return query, state
+
+    def cigar_mismatch(self, cigar, aln_off, ref_start, bases, ref_off, ref_len, qry_off, qry_len, cap=None, n_ops=None):
+        """The mismatching columns of a batch of alignments (svx_cigar_mismatch in include/svx.h): dict(aln, ref_pos,
+        qry_pos: uint32; ref_base, qry_base: uint8, upper case), ascending by (alignment, ref_pos).  `bases`: one uint8
+        pool holding alignment a's reference window at ref_off[a] (ref_len[a] bytes, from ref_start[a]) and its SEQ at
+        qry_off[a] (qry_len[a] bytes).  `cigar` / `n_ops` as for cigar_lift.  `cap` is a first guess: the call is repeated
+        with the exact count when it was too small, as cigar_extract does."""
+        aln_off = _as(aln_off, np.uint64)
+        ref_start = _as(ref_start, np.int32)
+        bases = _as(bases, np.uint8)
+        ref_off, qry_off = _as(ref_off, np.uint64), _as(qry_off, np.uint64)
+        ref_len, qry_len = _as(ref_len, np.uint32), _as(qry_len, np.uint32)
+        n_aln = len(aln_off) - 1 if len(aln_off) else 0
+        if any(len(x) != n_aln for x in (ref_start, ref_off, ref_len, qry_off, qry_len)):
+            raise SvxError(SVX_E_INVALID, "one ref_start, ref_off, ref_len, qry_off and qry_len per alignment")
+        if n_ops is None:
+            cigar = _as(cigar, np.uint32)
+            if n_aln and len(cigar) < int(aln_off[-1]):
+                raise SvxError(SVX_E_INVALID, "cigar shorter than aln_off[-1]")
+        if len(aln_off) == 0:
+            aln_off = np.zeros(1, np.uint64)
+        if cap is None:
+            cap = max(1024, len(bases) // 256)
+        while True:
+            cap = int(cap)
+            out = {"aln": np.empty(cap, np.uint32), "ref_pos": np.empty(cap, np.uint32), "qry_pos": np.empty(cap, np.uint32),
+                   "ref_base": np.empty(cap, np.uint8), "qry_base": np.empty(cap, np.uint8)}
+            soa = MismatchSoa(*(_ptr(out[k]) for k in ("aln", "ref_pos", "qry_pos", "ref_base", "qry_base")))
+            n = C.c_uint64(0)
+            tail = (_ptr(aln_off), _ptr(ref_start), n_aln, _ptr(bases), len(bases), _ptr(ref_off), _ptr(ref_len), _ptr(qry_off),
+                    _ptr(qry_len), soa, cap, C.byref(n))
+            if n_ops is None:
+                rc = self.lib.svx_cigar_mismatch(self.h, _ptr(cigar), *tail)
+            else:
+                rc = self.lib.svx_cigar_mismatch_dev(self.h, cigar, int(n_ops), *tail)
+            if rc == SVX_E_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(rc)
+            k = min(int(n.value), cap)
+            return {key: v[:k] for key, v in out.items()}
 
     def cover_single(self, start_key, end_key, list_off):
         """The ranges on which exactly ONE entry of a list — and the same one throughout — lies over the reference, per

@@ -27,9 +27,7 @@ static_assert(kPer * kThreads == SVX_LIFT_CHUNK && kPer == 4, "four ops per thre
 constexpr uint64_t kMaxChunks = 0x7FFFFFFFull;  // gridDim.x
 
 // (reference, query) bases; (0, 0) is the sum's identity
-struct Use {
-    uint64_t ref, qry;
-};
+using Use = svx_use;
 struct OpUse {
     __device__ __forceinline__ Use operator()(Use a, Use b) const { return Use{a.ref + b.ref, a.qry + b.qry}; }
 };
@@ -147,15 +145,8 @@ __global__ __launch_bounds__(kThreads) void k_lift_query(const uint32_t* __restr
 
 // the host-side refusals of both entries
 int check_lift(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln, const uint32_t* q_aln, uint32_t n_q) {
-    if (aln_off[0] != 0) {
-        SVX_SET_ERR(ctx, "%s: aln_off[0] is %llu, not 0", who, (unsigned long long)aln_off[0]);
-        return SVX_E_INVALID;
-    }
-    for (uint32_t a = 0; a < n_aln; ++a)
-        if (aln_off[a + 1] < aln_off[a]) {
-            SVX_SET_ERR(ctx, "%s: aln_off decreases at alignment %u", who, a);
-            return SVX_E_INVALID;
-        }
+    const int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln);
+    if (rc != SVX_OK) return rc;
     for (uint32_t q = 0; q < n_q; ++q)
         if (q_aln[q] >= n_aln) {
             SVX_SET_ERR(ctx, "%s: query %u names alignment %u of %u", who, q, q_aln[q], n_aln);
@@ -218,12 +209,8 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
     if (rc != SVX_OK) return rc;
     rc = svx_timing_mark(ctx, 1);
     if (rc != SVX_OK) return rc;
-    hipLaunchKernelGGL(k_lift_sums, dim3((uint32_t)n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_sum);
-    SVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_lift_chunks, dim3(1), dim3(kThreads), 0, ctx->stream, d_sum, (uint32_t)n_chunks, d_base);
-    SVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_lift_apply, dim3((uint32_t)n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_base, d_pref, d_pqry);
-    SVX_HIP(ctx, hipGetLastError());
+    rc = svx_lift_prefixes(ctx, d_cigar, n_ops, d_sum, d_base, d_pref, d_pqry);
+    if (rc != SVX_OK) return rc;
     rc = svx_timing_mark(ctx, 2);
     if (rc != SVX_OK) return rc;
     hipLaunchKernelGGL(k_lift_query, dim3((n_q + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, d_cigar, d_off, d_start, d_pref,
@@ -238,6 +225,38 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
 }
 
 }  // namespace
+
+// ---- what svx_mismatch.hip shares with this file (svx_internal.h)
+int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln) {
+    if (aln_off[0] != 0) {
+        SVX_SET_ERR(ctx, "%s: aln_off[0] is %llu, not 0", who, (unsigned long long)aln_off[0]);
+        return SVX_E_INVALID;
+    }
+    for (uint32_t a = 0; a < n_aln; ++a)
+        if (aln_off[a + 1] < aln_off[a]) {
+            SVX_SET_ERR(ctx, "%s: aln_off decreases at alignment %u", who, a);
+            return SVX_E_INVALID;
+        }
+    return SVX_OK;
+}
+
+int svx_lift_prefixes(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, svx_use* d_sum, svx_use* d_base, uint64_t* d_pref,
+                      uint64_t* d_pqry) {
+    const uint32_t n_chunks = (uint32_t)((n_ops + SVX_LIFT_CHUNK - 1) / SVX_LIFT_CHUNK);
+    hipLaunchKernelGGL(k_lift_sums, dim3(n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_sum);
+    SVX_HIP(ctx, hipGetLastError());
+    int rc = svx_lift_exclusive(ctx, d_sum, n_chunks, d_base);
+    if (rc != SVX_OK) return rc;
+    hipLaunchKernelGGL(k_lift_apply, dim3(n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_base, d_pref, d_pqry);
+    SVX_HIP(ctx, hipGetLastError());
+    return SVX_OK;
+}
+
+int svx_lift_exclusive(svx_ctx* ctx, const svx_use* d_in, uint32_t n, svx_use* d_out) {
+    hipLaunchKernelGGL(k_lift_chunks, dim3(1), dim3(kThreads), 0, ctx->stream, d_in, n, d_out);
+    SVX_HIP(ctx, hipGetLastError());
+    return SVX_OK;
+}
 
 extern "C" int svx_cigar_lift(svx_ctx* ctx, const uint32_t* cigar, const uint64_t* aln_off, const int32_t* ref_start, uint32_t n_aln,
                               const uint32_t* q_aln, const int64_t* q_ref, uint32_t n_q, uint32_t* out_query, uint8_t* out_state) {
