@@ -9,18 +9,17 @@
 // because an interval on an earlier contig ends below every key of the window's contig and one on a later contig
 // starts above lo (intervals and windows never cross a contig: the entry refuses those).  The intervals with
 // start <= lo are a PREFIX of the sorted list, so two launches answer the batch:
-//   k_cover_scan    one workgroup per list: inclusive prefix maximum of the end keys, kChunk elements per pass
-//                   (kPer consecutive ones per thread, DPP scan of the thread maxima across the wave, the waves'
-//                   maxima through LDS, the running maximum carried from pass to pass), into the context workspace;
+//   k_cover_scan    one workgroup per list: the carried scan of svx_scan_dev.h under max over the end keys, into the
+//                   context workspace;
 //   k_cover_search  one lane per window, the lists in turn: upper bound of lo among the start keys (the list is read
 //                   through L2, neighbouring lanes share the upper levels of the search), one compare with the prefix
 //                   maximum in front of it, one byte out — consecutive lanes, consecutive bytes.
 // Every word of the prefix maxima is written by the scan before the search reads it, and only inside the lists'
 // ranges: nothing depends on what the workspace held (the scratch contract, include/svx.h).
 //
-// svx_cover_locate answers the same batch with WHICH entry covers: k_locate_scan is k_cover_scan over
-// (end key, list-local index) pairs under arg-max — the lowest index among equal keys —, k_locate_search writes the index
-// in front of the upper bound where its key reaches hi, SVX_COVER_NONE elsewhere.
+// svx_cover_locate answers the same batch with WHICH entry covers: k_locate_scan is the carried scan under
+// arg-max over (end key, list-local index) pairs — the lowest index among equal keys —, k_locate_search the same search
+// that writes the index in front of the upper bound where its key reaches hi, SVX_COVER_NONE elsewhere.
 //
 // svx_cover_single asks of the same lists where EXACTLY one entry lies over the reference: the maximal
 // ranges on which one entry, and the same one, is the only one with start <= p < end.  With the entries in start order
@@ -31,7 +30,7 @@
 //                     the four" on the same ladder — NOT idempotent, so every combine is over disjoint lane ranges —,
 //                     one candidate segment per slot, a flag, the workgroup's exclusive sum of the flags with a running
 //                     count, the segments compacted list-locally into the workspace at list_off[l] + rank; the count;
-//   k_single_offsets  one workgroup: seg_off = exclusive sum of the counts over the lists;
+//   k_single_offsets  one workgroup: seg_off = exclusive sum of the counts over the lists, the carried scan under sum;
 //   k_single_pack     every list's segments to their final contiguous place.
 // A list's pack reads the `count` words its scan wrote and nothing else.
 #include "svx_internal.h"
@@ -40,9 +39,9 @@
 namespace {
 
 constexpr int kThreads = kScanThreads;
-constexpr int kPer = SVX_COVER_SCAN_CHUNK / kThreads;  // consecutive elements of one thread
+constexpr int kPer = kScanPer;  // consecutive elements of one thread
 constexpr int kWaves = kScanWaves;
-static_assert(kPer * kThreads == SVX_COVER_SCAN_CHUNK && kPer == 4, "four elements per thread, loaded as two 16-byte words");
+static_assert(SVX_COVER_SCAN_CHUNK == kScanChunk, "the public chunk is one pass of the carried scan");
 constexpr uint32_t kMaxGridY = 65535;
 
 // the two largest end keys of a set of entries, m1 >= m2; (0, 0): no entry
@@ -66,41 +65,27 @@ struct OpArgMax {
         return (a.key > b.key || (a.key == b.key && a.idx <= b.idx)) ? a : b;
     }
 };
-// inclusive maximum over the lanes 0..l of the wave
-__device__ __forceinline__ uint64_t wave_scan_max(uint64_t v) { return wave_scan(v, OpMax()); }
 
 __global__ __launch_bounds__(kThreads) void k_cover_scan(const uint64_t* __restrict__ end_key, const uint64_t* __restrict__ list_off,
                                                          uint64_t* __restrict__ pmax) {
     __shared__ uint64_t s_wave[2][kWaves];
-    const uint64_t lo = list_off[blockIdx.x], hi = list_off[blockIdx.x + 1];
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
-    uint64_t carry = 0;
-    int slot = 0;
-    // (the trip count depends on the list alone: every lane of the group takes every pass, DPP and barrier included)
-    for (uint64_t base = lo; base < hi; base += SVX_COVER_SCAN_CHUNK, slot ^= 1) {
-        const uint64_t first = base + (uint64_t)tid * kPer;
-        uint64_t v[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) v[j] = first + j < hi ? end_key[first + j] : 0;
-#pragma unroll
-        for (int j = 1; j < kPer; ++j) v[j] = max64(v[j], v[j - 1]);
-        const uint64_t incl = wave_scan_max(v[kPer - 1]);
-        if ((tid & 63) == 63) s_wave[slot][wave] = incl;
-        // the lanes in front of this one: wave_shr:1, lane 0 receives 0
-        uint64_t before = dpp0_64<0x138, 0xF>(incl);
-        __syncthreads();  // (two buffers in turn: the next write of this one is behind the next pass's barrier)
-        uint64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const uint64_t t = s_wave[slot][w];
-            if (w < wave) before = max64(before, t);
-            total = max64(total, t);
-        }
-        before = max64(before, carry);
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-            if (first + j < hi) pmax[first + j] = max64(v[j], before);
-        carry = max64(carry, total);
+    carried_scan(list_off[blockIdx.x], list_off[blockIdx.x + 1], OpMax(), [=](uint64_t i) { return end_key[i]; },
+                 [=](uint64_t i, uint64_t, uint64_t incl) { pmax[i] = incl; }, s_wave);
+}
+
+// one lane per query, the lists in turn: answer(i, hi) of the last entry i with start key <= lo, `none` where the list has
+// no such entry
+template <typename Out, typename Answer>
+__device__ __forceinline__ void search_lists(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ list_off, uint32_t n_lists,
+                                             const uint64_t* __restrict__ q_lo, const uint64_t* __restrict__ q_hi, uint32_t n_q,
+                                             Out* __restrict__ out, Out none, Answer answer) {
+    const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
+    if (q >= n_q) return;
+    const uint64_t lo = q_lo[q], hi = q_hi[q];
+    for (uint32_t l = blockIdx.y; l < n_lists; l += gridDim.y) {
+        const uint64_t b = list_off[l];
+        const uint64_t a = upper_bound(start_key, b, list_off[l + 1], lo);
+        out[(size_t)l * n_q + q] = a > b ? answer(a - 1, hi) : none;
     }
 }
 
@@ -108,79 +93,29 @@ __global__ __launch_bounds__(kThreads) void k_cover_search(const uint64_t* __res
                                                            const uint64_t* __restrict__ list_off, uint32_t n_lists,
                                                            const uint64_t* __restrict__ q_lo, const uint64_t* __restrict__ q_hi,
                                                            uint32_t n_q, uint8_t* __restrict__ out) {
-    const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
-    if (q >= n_q) return;
-    const uint64_t lo = q_lo[q], hi = q_hi[q];
-    for (uint32_t l = blockIdx.y; l < n_lists; l += gridDim.y) {
-        const uint64_t b = list_off[l], e = list_off[l + 1];
-        // first element with start_key > lo
-        uint64_t a = b, n = e - b;
-        while (n) {
-            const uint64_t half = n >> 1;
-            if (start_key[a + half] <= lo) { a += half + 1; n -= half + 1; } else n = half;
-        }
-        out[(size_t)l * n_q + q] = (a > b && pmax[a - 1] >= hi) ? 1 : 0;
-    }
+    search_lists(start_key, list_off, n_lists, q_lo, q_hi, n_q, out, (uint8_t)0,
+                 [=](uint64_t i, uint64_t hi) { return (uint8_t)(pmax[i] >= hi ? 1 : 0); });
 }
 
-// svx_cover_locate: k_cover_scan as a prefix ARG-max — the same passes, the same fold of the waves through LDS, the same
-// carry, over (end key, list-local index) pairs; amax / aidx[i]: the pair of the list's entries up to i
+// svx_cover_locate: amax / aidx[i] is the arg-max pair of the list's entries up to i
 __global__ __launch_bounds__(kThreads) void k_locate_scan(const uint64_t* __restrict__ end_key, const uint64_t* __restrict__ list_off,
                                                           uint64_t* __restrict__ amax, uint32_t* __restrict__ aidx) {
     __shared__ ArgMax s_wave[2][kWaves];
-    const uint64_t lo = list_off[blockIdx.x], hi = list_off[blockIdx.x + 1];
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
-    const OpArgMax op;
-    ArgMax carry = ArgMax{0, 0, 0};
-    int slot = 0;
-    // (the trip count depends on the list alone: every lane of the group takes every pass, DPP and barrier included)
-    for (uint64_t base = lo; base < hi; base += SVX_COVER_SCAN_CHUNK, slot ^= 1) {
-        const uint64_t first = base + (uint64_t)tid * kPer;
-        ArgMax v[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) v[j] = first + j < hi ? ArgMax{end_key[first + j], (uint32_t)(first + j - lo), 0} : ArgMax{0, 0, 0};
-#pragma unroll
-        for (int j = 1; j < kPer; ++j) v[j] = op(v[j - 1], v[j]);
-        const ArgMax incl = wave_scan(v[kPer - 1], op);
-        if ((tid & 63) == 63) s_wave[slot][wave] = incl;
-        ArgMax before = dpp0<0x138, 0xF>(incl);  // wave_shr:1, lane 0 receives (0, 0)
-        __syncthreads();  // (two buffers in turn, as in k_cover_scan)
-        ArgMax total = ArgMax{0, 0, 0};
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const ArgMax t = s_wave[slot][w];
-            if (w < wave) before = op(before, t);
-            total = op(total, t);
-        }
-        before = op(before, carry);
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-            if (first + j < hi) {
-                const ArgMax m = op(before, v[j]);
-                amax[first + j] = m.key;
-                aidx[first + j] = m.idx;
-            }
-        carry = op(carry, total);
-    }
+    const uint64_t lo = list_off[blockIdx.x];
+    carried_scan(lo, list_off[blockIdx.x + 1], OpArgMax(), [=](uint64_t i) { return ArgMax{end_key[i], (uint32_t)(i - lo), 0}; },
+                 [=](uint64_t i, ArgMax, ArgMax incl) {
+                     amax[i] = incl.key;
+                     aidx[i] = incl.idx;
+                 },
+                 s_wave);
 }
 
 __global__ __launch_bounds__(kThreads) void k_locate_search(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ amax,
                                                             const uint32_t* __restrict__ aidx, const uint64_t* __restrict__ list_off,
                                                             uint32_t n_lists, const uint64_t* __restrict__ q_lo,
                                                             const uint64_t* __restrict__ q_hi, uint32_t n_q, uint32_t* __restrict__ out) {
-    const uint32_t q = blockIdx.x * kThreads + threadIdx.x;
-    if (q >= n_q) return;
-    const uint64_t lo = q_lo[q], hi = q_hi[q];
-    for (uint32_t l = blockIdx.y; l < n_lists; l += gridDim.y) {
-        const uint64_t b = list_off[l], e = list_off[l + 1];
-        // first element with start_key > lo
-        uint64_t a = b, n = e - b;
-        while (n) {
-            const uint64_t half = n >> 1;
-            if (start_key[a + half] <= lo) { a += half + 1; n -= half + 1; } else n = half;
-        }
-        out[(size_t)l * n_q + q] = (a > b && amax[a - 1] >= hi) ? aidx[a - 1] : SVX_COVER_NONE;
-    }
+    search_lists(start_key, list_off, n_lists, q_lo, q_hi, n_q, out, (uint32_t)SVX_COVER_NONE,
+                 [=](uint64_t i, uint64_t hi) { return amax[i] >= hi ? aidx[i] : (uint32_t)SVX_COVER_NONE; });
 }
 
 __global__ __launch_bounds__(kThreads) void k_single_scan(const uint64_t* __restrict__ start_key, const uint64_t* __restrict__ end_key,
@@ -236,28 +171,13 @@ __global__ __launch_bounds__(kThreads) void k_single_scan(const uint64_t* __rest
     if (tid == 0) count[blockIdx.x] = written;
 }
 
-// seg_off[0] = 0, seg_off[l + 1] = count[0] + .. + count[l]: one workgroup, kChunk lists per pass
+// seg_off[0] = 0, seg_off[l + 1] = count[0] + .. + count[l]: one workgroup
 __global__ __launch_bounds__(kThreads) void k_single_offsets(const uint64_t* __restrict__ count, uint32_t n_lists,
                                                              uint64_t* __restrict__ seg_off) {
-    __shared__ uint64_t s_cnt[kWaves];
-    const int tid = (int)threadIdx.x;
-    uint64_t carry = 0;
-    if (tid == 0) seg_off[0] = 0;
-    for (uint32_t base = 0; base < n_lists; base += SVX_COVER_SCAN_CHUNK) {
-        const uint32_t first = base + (uint32_t)tid * kPer;
-        uint64_t v[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) v[j] = first + j < n_lists ? count[first + j] : 0;
-#pragma unroll
-        for (int j = 1; j < kPer; ++j) v[j] += v[j - 1];
-        uint64_t total;
-        const uint64_t before = group_before(wave_scan(v[kPer - 1], OpAdd()), s_cnt, tid, OpAdd(), &total) + carry;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-            if (first + j < n_lists) seg_off[first + j + 1] = v[j] + before;
-        carry += total;
-        __syncthreads();
-    }
+    __shared__ uint64_t s_wave[2][kWaves];
+    if (threadIdx.x == 0) seg_off[0] = 0;
+    carried_scan(0, n_lists, OpAdd(), [=](uint64_t i) { return count[i]; },
+                 [=](uint64_t i, uint64_t, uint64_t incl) { seg_off[i + 1] = incl; }, s_wave);
 }
 
 __global__ __launch_bounds__(kThreads) void k_single_pack(const uint64_t* __restrict__ list_off, const uint64_t* __restrict__ seg_off,
@@ -326,109 +246,95 @@ int check_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
     return SVX_OK;
 }
 
-}  // namespace
+// the lists of a batch in the stage: what all three entries upload (lists_bytes of the caller's reserve)
+struct DevLists {
+    uint64_t *start, *end, *off;
+};
+size_t lists_bytes(uint64_t n, uint32_t n_lists) { return 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8); }
+int upload_lists(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off, uint32_t n_lists,
+                 DevLists* d) {
+    const uint64_t n = list_off[n_lists];
+    d->start = svx_stage_take<uint64_t>(ctx, n);
+    d->end = svx_stage_take<uint64_t>(ctx, n);
+    d->off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    SVX_HIP(ctx, hipMemcpyAsync(d->start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d->end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(d->off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    return SVX_OK;
+}
 
-extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
-                               uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out) {
+// svx_cover_query (one byte per answer, prefix maxima alone in the workspace) and svx_cover_locate (`locate`: four bytes
+// per answer, the prefix arg-max's index array beside the maxima, lists of at most `list_limit` entries); `fill`: the byte
+// of every answer where all lists are empty
+int cover_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, void* out, bool locate, uint64_t list_limit,
+                int fill) {
     if (!ctx) return SVX_E_INVALID;
     if (n_lists == 0 || n_q == 0) return SVX_OK;
-    int rc = check_batch(ctx, "svx_cover_query", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
+    int rc = check_batch(ctx, who, start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
     if (rc != SVX_OK) return rc;
     const uint64_t n = list_off[n_lists];
-    const size_t n_out = (size_t)n_lists * n_q;
+    for (uint32_t l = 0; l < n_lists; ++l)
+        if (list_off[l + 1] - list_off[l] > list_limit) {
+            SVX_SET_ERR(ctx, "%s: list %u has %llu entries", who, l, (unsigned long long)(list_off[l + 1] - list_off[l]));
+            return SVX_E_TOO_LARGE;
+        }
+    const size_t out_elem = locate ? 4 : 1, n_out = (size_t)n_lists * n_q;
     if (n == 0) {  // empty lists only
-        memset(out, 0, n_out);
+        memset(out, fill, n_out * out_elem);
         return SVX_OK;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8) + 2 * svx_take_bytes(n_q, 8) +
-                                        svx_take_bytes(n_out, 1));
+    rc = svx_stage_reserve(ctx, lists_bytes(n, n_lists) + 2 * svx_take_bytes(n_q, 8) + svx_take_bytes(n_out, out_elem));
     if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8));
+    rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8) + (locate ? svx_take_bytes(n, 4) : 0));
     if (rc != SVX_OK) return rc;
-    uint64_t* d_start = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_end = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    DevLists d;
+    rc = upload_lists(ctx, start_key, end_key, list_off, n_lists, &d);
+    if (rc != SVX_OK) return rc;
     uint64_t* d_lo = svx_stage_take<uint64_t>(ctx, n_q);
     uint64_t* d_hi = svx_stage_take<uint64_t>(ctx, n_q);
-    uint8_t* d_out = svx_stage_take<uint8_t>(ctx, n_out);
-    uint64_t* d_pmax = svx_ws_take<uint64_t>(ctx, n);
-    SVX_HIP(ctx, hipMemcpyAsync(d_start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint8_t* d_out = svx_stage_take<uint8_t>(ctx, n_out * out_elem);
+    uint64_t* d_max = svx_ws_take<uint64_t>(ctx, n);
+    uint32_t* d_idx = locate ? svx_ws_take<uint32_t>(ctx, n) : nullptr;
     SVX_HIP(ctx, hipMemcpyAsync(d_lo, q_lo, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
     SVX_HIP(ctx, hipMemcpyAsync(d_hi, q_hi, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
     rc = svx_timing_begin(ctx);
     if (rc != SVX_OK) return rc;
-    hipLaunchKernelGGL(k_cover_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d_end, d_off, d_pmax);
+    if (locate)
+        hipLaunchKernelGGL(k_locate_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.end, d.off, d_max, d_idx);
+    else
+        hipLaunchKernelGGL(k_cover_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.end, d.off, d_max);
     SVX_HIP(ctx, hipGetLastError());
     rc = svx_timing_mark(ctx, 1);
     if (rc != SVX_OK) return rc;
     const dim3 grid((n_q + kThreads - 1) / kThreads, n_lists < kMaxGridY ? n_lists : kMaxGridY);
-    hipLaunchKernelGGL(k_cover_search, grid, dim3(kThreads), 0, ctx->stream, d_start, d_pmax, d_off, n_lists, d_lo, d_hi, n_q, d_out);
+    if (locate)
+        hipLaunchKernelGGL(k_locate_search, grid, dim3(kThreads), 0, ctx->stream, d.start, d_max, d_idx, d.off, n_lists, d_lo, d_hi, n_q,
+                           reinterpret_cast<uint32_t*>(d_out));
+    else
+        hipLaunchKernelGGL(k_cover_search, grid, dim3(kThreads), 0, ctx->stream, d.start, d_max, d.off, n_lists, d_lo, d_hi, n_q, d_out);
     SVX_HIP(ctx, hipGetLastError());
     rc = svx_timing_mark(ctx, 2);
     if (rc != SVX_OK) return rc;
     rc = svx_timing_end(ctx);
     if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out * out_elem, hipMemcpyDeviceToHost, ctx->stream));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }
 
+}  // namespace
+
+extern "C" int svx_cover_query(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
+                               uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint8_t* out) {
+    return cover_batch(ctx, "svx_cover_query", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out, false, UINT64_MAX, 0);
+}
+
 extern "C" int svx_cover_locate(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
                                 uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, uint32_t* out) {
-    if (!ctx) return SVX_E_INVALID;
-    if (n_lists == 0 || n_q == 0) return SVX_OK;
-    int rc = check_batch(ctx, "svx_cover_locate", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
-    if (rc != SVX_OK) return rc;
-    const uint64_t n = list_off[n_lists];
-    for (uint32_t l = 0; l < n_lists; ++l)
-        if (list_off[l + 1] - list_off[l] >= SVX_COVER_NONE) {  // (an index has to differ from "none")
-            SVX_SET_ERR(ctx, "svx_cover_locate: list %u has %llu entries", l, (unsigned long long)(list_off[l + 1] - list_off[l]));
-            return SVX_E_TOO_LARGE;
-        }
-    const size_t n_out = (size_t)n_lists * n_q;
-    if (n == 0) {  // empty lists only
-        memset(out, 0xFF, n_out * 4);
-        return SVX_OK;
-    }
-    SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8) + 2 * svx_take_bytes(n_q, 8) +
-                                        svx_take_bytes(n_out, 4));
-    if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8) + svx_take_bytes(n, 4));
-    if (rc != SVX_OK) return rc;
-    uint64_t* d_start = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_end = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
-    uint64_t* d_lo = svx_stage_take<uint64_t>(ctx, n_q);
-    uint64_t* d_hi = svx_stage_take<uint64_t>(ctx, n_q);
-    uint32_t* d_out = svx_stage_take<uint32_t>(ctx, n_out);
-    uint64_t* d_amax = svx_ws_take<uint64_t>(ctx, n);
-    uint32_t* d_aidx = svx_ws_take<uint32_t>(ctx, n);
-    SVX_HIP(ctx, hipMemcpyAsync(d_start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_lo, q_lo, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_hi, q_hi, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    hipLaunchKernelGGL(k_locate_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d_end, d_off, d_amax, d_aidx);
-    SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    const dim3 grid((n_q + kThreads - 1) / kThreads, n_lists < kMaxGridY ? n_lists : kMaxGridY);
-    hipLaunchKernelGGL(k_locate_search, grid, dim3(kThreads), 0, ctx->stream, d_start, d_amax, d_aidx, d_off, n_lists, d_lo, d_hi, n_q,
-                       d_out);
-    SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SVX_OK;
+    // (an index has to differ from "none")
+    return cover_batch(ctx, "svx_cover_locate", start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out, true, SVX_COVER_NONE - 1u, 0xFF);
 }
 
 extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
@@ -450,33 +356,30 @@ extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const u
         return SVX_E_TOO_LARGE;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, 4 * svx_take_bytes(n, 8) + 2 * svx_take_bytes((size_t)n_lists + 1, 8));
+    rc = svx_stage_reserve(ctx, lists_bytes(n, n_lists) + 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8));
     if (rc != SVX_OK) return rc;
     rc = svx_ws_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes(n_lists, 8));
     if (rc != SVX_OK) return rc;
-    uint64_t* d_start = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_end = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
+    DevLists d;
+    rc = upload_lists(ctx, start_key, end_key, list_off, n_lists, &d);
+    if (rc != SVX_OK) return rc;
     uint64_t* d_seg_lo = svx_stage_take<uint64_t>(ctx, n);
     uint64_t* d_seg_hi = svx_stage_take<uint64_t>(ctx, n);
     uint64_t* d_seg_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
     uint64_t* d_loc_lo = svx_ws_take<uint64_t>(ctx, n);
     uint64_t* d_loc_hi = svx_ws_take<uint64_t>(ctx, n);
     uint64_t* d_count = svx_ws_take<uint64_t>(ctx, n_lists);
-    SVX_HIP(ctx, hipMemcpyAsync(d_start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     rc = svx_timing_begin(ctx);
     if (rc != SVX_OK) return rc;
     rc = svx_timing_mark(ctx, 1);
     if (rc != SVX_OK) return rc;
-    hipLaunchKernelGGL(k_single_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d_start, d_end, d_off, d_loc_lo, d_loc_hi, d_count);
+    hipLaunchKernelGGL(k_single_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.start, d.end, d.off, d_loc_lo, d_loc_hi, d_count);
     SVX_HIP(ctx, hipGetLastError());
     rc = svx_timing_mark(ctx, 2);
     if (rc != SVX_OK) return rc;
     hipLaunchKernelGGL(k_single_offsets, dim3(1), dim3(kThreads), 0, ctx->stream, d_count, n_lists, d_seg_off);
     SVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_single_pack, dim3(n_lists, kPackGridY), dim3(kThreads), 0, ctx->stream, d_off, d_seg_off, d_loc_lo, d_loc_hi,
+    hipLaunchKernelGGL(k_single_pack, dim3(n_lists, kPackGridY), dim3(kThreads), 0, ctx->stream, d.off, d_seg_off, d_loc_lo, d_loc_hi,
                        d_seg_lo, d_seg_hi);
     SVX_HIP(ctx, hipGetLastError());
     rc = svx_timing_end(ctx);

@@ -124,15 +124,17 @@ static inline size_t svx_take_bytes(size_t count, size_t elem) {
     return svx_align_up(count * elem, 256) + 256;
 }
 
-// svx_lift.hip, shared with svx_mismatch.hip: aln_off[0] == 0 and non-decreasing offsets, else SVX_E_INVALID with a message
-// naming the alignment; the scan of an op pool's (reference, query) consumption in three launches — per-chunk sums into
+// svx_lift.hip, shared with svx_mismatch.hip: aln_off[0] == 0, non-decreasing offsets and *n_ops = aln_off[n_aln] inside the
+// pool (host words `cigar`, or `pool_ops` words at d_pool when that is not null), else SVX_E_INVALID with a message naming
+// the alignment or the end; the scan of an op pool's (reference, query) consumption in three launches — per-chunk sums into
 // d_sum, their exclusive scan into d_base (ceil(n_ops / SVX_LIFT_CHUNK) entries each, n_ops >= 1 and at most 2^31 - 1 chunks),
 // the inclusive 64-bit prefixes of both per op into d_pref / d_pqry —; and the middle launch alone: ONE workgroup's
 // exclusive scan of n (reference, query) sums, d_out[k] = d_in[0] + .. + d_in[k - 1].
 struct svx_use {
     uint64_t ref, qry;
 };
-int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln);
+int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln, const uint32_t* cigar,
+                           const uint32_t* d_pool, uint64_t pool_ops, uint64_t* n_ops);
 int svx_lift_prefixes(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, svx_use* d_sum, svx_use* d_base, uint64_t* d_pref,
                       uint64_t* d_pqry);
 int svx_lift_exclusive(svx_ctx* ctx, const svx_use* d_in, uint32_t n, svx_use* d_out);

@@ -8,11 +8,10 @@
 // less the alignment's base.  So a plain reduce-then-scan over the pool and one binary search per query answer the batch,
 // in four launches with nothing handed between workgroups inside one:
 //   k_lift_sums    one workgroup per chunk of SVX_LIFT_CHUNK ops: the chunk's (reference, query) sum;
-//   k_lift_chunks  ONE workgroup: exclusive scan of the chunk sums, SVX_LIFT_CHUNK of them per pass, the running sum
-//                  carried from pass to pass (k_single_offsets' shape);
+//   k_lift_chunks  ONE workgroup: exclusive prefixes of the chunk sums, the carried scan of svx_scan_dev.h under sum;
 //   k_lift_apply   one workgroup per chunk: the ops' consumption again, scanned inside the workgroup on the ladder of
 //                  svx_scan_dev.h, plus the chunk's base: P_ref and P_qry, 64 bits each, into the context workspace;
-//   k_lift_query   one lane per query: upper bound among the alignment's P_ref, for END one lower bound more.
+//   k_lift_query   one lane per query: upper bound among the alignment's P_ref, for END one more.
 // The prefixes are 64 bits wide: forty alignments of 2^27 reference bases pass 2^32.  Every word of the chunk sums, the
 // chunk bases and the prefixes is written before the launch that reads it starts, and only words inside [0, n_ops) and
 // [0, n_chunks) are read: nothing depends on what the workspace held (the scratch contract, include/svx.h).
@@ -22,8 +21,8 @@
 namespace {
 
 constexpr int kThreads = kScanThreads;
-constexpr int kPer = SVX_LIFT_CHUNK / kThreads;
-static_assert(kPer * kThreads == SVX_LIFT_CHUNK && kPer == 4, "four ops per thread");
+constexpr int kPer = kScanPer;
+static_assert(SVX_LIFT_CHUNK == kScanChunk, "the public chunk is one workgroup's ops and one pass of the carried scan");
 constexpr uint64_t kMaxChunks = 0x7FFFFFFFull;  // gridDim.x
 
 // (reference, query) bases; (0, 0) is the sum's identity
@@ -57,27 +56,11 @@ __global__ __launch_bounds__(kThreads) void k_lift_sums(const uint32_t* __restri
     if (tid == 0) chunk_sum[blockIdx.x] = total;
 }
 
-// chunk_base[c] = chunk_sum[0] + .. + chunk_sum[c - 1]: one workgroup, SVX_LIFT_CHUNK chunks per pass
+// chunk_base[c] = chunk_sum[0] + .. + chunk_sum[c - 1]: one workgroup
 __global__ __launch_bounds__(kThreads) void k_lift_chunks(const Use* __restrict__ chunk_sum, uint32_t n_chunks, Use* __restrict__ chunk_base) {
-    __shared__ Use s_w[kScanWaves];
-    const int tid = (int)threadIdx.x;
-    Use carry = Use{0, 0};
-    // (the trip count depends on n_chunks alone: every lane takes every pass, DPP and barriers included)
-    for (uint32_t base = 0; base < n_chunks; base += SVX_LIFT_CHUNK) {
-        const uint32_t first = base + (uint32_t)tid * kPer;
-        Use v[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) v[j] = first + j < n_chunks ? chunk_sum[first + j] : Use{0, 0};
-#pragma unroll
-        for (int j = 1; j < kPer; ++j) v[j] = OpUse()(v[j - 1], v[j]);
-        Use total;
-        const Use before = OpUse()(group_before(wave_scan(v[kPer - 1], OpUse()), s_w, tid, OpUse(), &total), carry);
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-            if (first + j < n_chunks) chunk_base[first + j] = j ? OpUse()(before, v[j - 1]) : before;
-        carry = OpUse()(carry, total);
-        __syncthreads();  // (s_w is written again in the next pass)
-    }
+    __shared__ Use s_wave[2][kScanWaves];
+    carried_scan(0, n_chunks, OpUse(), [=](uint64_t i) { return chunk_sum[i]; }, [=](uint64_t i, Use before, Use) { chunk_base[i] = before; },
+                 s_wave);
 }
 
 __global__ __launch_bounds__(kThreads) void k_lift_apply(const uint32_t* __restrict__ cigar, uint64_t n_ops, const Use* __restrict__ chunk_base,
@@ -114,12 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_lift_query(const uint32_t* __restr
         const uint64_t end_ref = p_ref[e - 1];
         const uint64_t target = base_ref + ((uint64_t)r - (uint64_t)start);  // (the difference < 2^63 + 2^31, base_ref < 2^60: no wrap)
         if (target < end_ref) {
-            // first op with P_ref > target
-            uint64_t a = b, n = e - b;
-            while (n) {
-                const uint64_t half = n >> 1;
-                if (p_ref[a + half] <= target) { a += half + 1; n -= half + 1; } else n = half;
-            }
+            const uint64_t a = upper_bound(p_ref, b, e, target);  // the first op with P_ref > target
             const uint64_t ref_before = a > b ? p_ref[a - 1] : base_ref, qry_before = (a > b ? p_qry[a - 1] : base_qry) - base_qry;
             if ((kQryOps >> (cigar[a] & 15u)) & 1u) {
                 query = (uint32_t)(qry_before + (target - ref_before));
@@ -129,12 +107,9 @@ __global__ __launch_bounds__(kThreads) void k_lift_query(const uint32_t* __restr
                 state = SVX_LIFT_DELETED;
             }
         } else if (target == end_ref && end_ref > base_ref) {
-            // the last op that consumes reference: the first one whose P_ref reaches the alignment's total
-            uint64_t a = b, n = e - b;
-            while (n) {
-                const uint64_t half = n >> 1;
-                if (p_ref[a + half] < end_ref) { a += half + 1; n -= half + 1; } else n = half;
-            }
+            // the last op that consumes reference: the first one whose P_ref reaches the alignment's total — on integers
+            // P_ref >= end_ref is P_ref > end_ref - 1, and end_ref > base_ref >= 0 here, so end_ref - 1 does not wrap
+            const uint64_t a = upper_bound(p_ref, b, e, end_ref - 1);
             query = (uint32_t)(p_qry[a] - base_qry);
             state = SVX_LIFT_END;
         }
@@ -144,8 +119,9 @@ __global__ __launch_bounds__(kThreads) void k_lift_query(const uint32_t* __restr
 }
 
 // the host-side refusals of both entries
-int check_lift(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln, const uint32_t* q_aln, uint32_t n_q) {
-    const int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln);
+int check_lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d_pool, uint64_t pool_ops, const uint64_t* aln_off,
+               uint32_t n_aln, const uint32_t* q_aln, uint32_t n_q, uint64_t* n_ops) {
+    const int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, n_ops);
     if (rc != SVX_OK) return rc;
     for (uint32_t q = 0; q < n_q; ++q)
         if (q_aln[q] >= n_aln) {
@@ -162,13 +138,9 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
     if (!ctx) return SVX_E_INVALID;
     if (n_q == 0) return SVX_OK;
     if (!aln_off || !q_aln || !q_ref || !out_query || !out_state || (n_aln && !ref_start)) return SVX_E_INVALID;
-    int rc = check_lift(ctx, who, aln_off, n_aln, q_aln, n_q);
+    uint64_t n_ops;
+    int rc = check_lift(ctx, who, cigar, d_pool, pool_ops, aln_off, n_aln, q_aln, n_q, &n_ops);
     if (rc != SVX_OK) return rc;
-    const uint64_t n_ops = aln_off[n_aln];
-    if (d_pool ? n_ops > pool_ops : (n_ops && !cigar)) {
-        SVX_SET_ERR(ctx, "%s: aln_off ends at %llu, behind the pool", who, (unsigned long long)n_ops);
-        return SVX_E_INVALID;
-    }
     if (n_ops == 0) {  // alignments without ops only
         memset(out_query, 0, (size_t)n_q * 4);
         memset(out_state, SVX_LIFT_OUTSIDE, n_q);
@@ -227,7 +199,8 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
 }  // namespace
 
 // ---- what svx_mismatch.hip shares with this file (svx_internal.h)
-int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln) {
+int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_off, uint32_t n_aln, const uint32_t* cigar,
+                           const uint32_t* d_pool, uint64_t pool_ops, uint64_t* n_ops) {
     if (aln_off[0] != 0) {
         SVX_SET_ERR(ctx, "%s: aln_off[0] is %llu, not 0", who, (unsigned long long)aln_off[0]);
         return SVX_E_INVALID;
@@ -237,6 +210,11 @@ int svx_lift_check_offsets(svx_ctx* ctx, const char* who, const uint64_t* aln_of
             SVX_SET_ERR(ctx, "%s: aln_off decreases at alignment %u", who, a);
             return SVX_E_INVALID;
         }
+    *n_ops = aln_off[n_aln];
+    if (d_pool ? *n_ops > pool_ops : (*n_ops && !cigar)) {
+        SVX_SET_ERR(ctx, "%s: aln_off ends at %llu, behind the pool", who, (unsigned long long)*n_ops);
+        return SVX_E_INVALID;
+    }
     return SVX_OK;
 }
 

@@ -36,20 +36,6 @@ static_assert(kCols * kThreads == SVX_MISMATCH_TILE && kCols == 16, "sixteen ref
 constexpr uint64_t kMaxTiles = 0x7FFFFFFEull;  // gridDim.x, and one entry more for the total
 constexpr size_t kPadFront = 16, kPadBack = 32;  // what the 16-byte loads may touch in front of and behind the pool
 
-struct OpAdd32 {
-    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
-};
-
-// first index in [lo, hi) with p[index] > target, hi when there is none
-__device__ __forceinline__ uint64_t upper_bound(const uint64_t* __restrict__ p, uint64_t lo, uint64_t hi, uint64_t target) {
-    uint64_t n = hi - lo;
-    while (n) {
-        const uint64_t half = n >> 1;
-        if (p[lo + half] <= target) { lo += half + 1; n -= half + 1; } else n = half;
-    }
-    return lo;
-}
-
 // the 16 bytes at p (any alignment) as four dwords, little endian: five aligned dwords, v_alignbyte
 __device__ __forceinline__ void load16(const uint8_t* __restrict__ p, uint32_t* v) {
     const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
@@ -194,13 +180,9 @@ int mismatch(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_
     if (n_aln && (!ref_start || !ref_off || !ref_len || !qry_off || !qry_len)) return SVX_E_INVALID;
     if (n_bases && !bases) return SVX_E_INVALID;
     if (cap && (!out.aln || !out.ref_pos || !out.qry_pos || !out.ref_base || !out.qry_base)) return SVX_E_INVALID;
-    int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln);
+    uint64_t n_ops;
+    int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, &n_ops);
     if (rc != SVX_OK) return rc;
-    const uint64_t n_ops = aln_off[n_aln];
-    if (d_pool ? n_ops > pool_ops : (n_ops && !cigar)) {
-        SVX_SET_ERR(ctx, "%s: aln_off ends at %llu, behind the pool", who, (unsigned long long)n_ops);
-        return SVX_E_INVALID;
-    }
     std::vector<uint64_t> tile_off((size_t)n_aln + 1, 0);
     uint64_t most = 0;  // no more events than columns inside both lengths
     for (uint32_t a = 0; a < n_aln; ++a) {

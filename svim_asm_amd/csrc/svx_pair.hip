@@ -35,6 +35,7 @@
 // dependent latencies (launches, grid barriers, LDS passes), not by bytes.  Determinism: ranks
 // come from prefix sums only; the histogram atomics are commutative counts.
 #include "svx_internal.h"
+#include "svx_scan_dev.h"
 
 namespace {
 
@@ -268,21 +269,8 @@ __device__ __forceinline__ uint64_t original_key(const KeyFields& f, uint64_t d)
     return k;
 }
 
-// DPP lane movement (gfx9 family): 0 flows into lanes without a source
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-// inclusive sum over the wave: shifts by 1, 2, 4, 8 inside the rows of 16, then lane 15 / lane 31 broadcasts
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
-    v += dpp0<0x111, 0xF>(v);
-    v += dpp0<0x112, 0xF>(v);
-    v += dpp0<0x114, 0xF>(v);
-    v += dpp0<0x118, 0xF>(v);
-    v += dpp0<0x142, 0xA>(v);
-    v += dpp0<0x143, 0xC>(v);
-    return v;
-}
+// inclusive sum over the wave: the DPP ladder of svx_scan_dev.h
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) { return wave_scan(v, OpAdd32()); }
 
 // inclusive scan of `v` over a 1024-thread workgroup; returns the scanned value, *total the sum.
 // TAIL_SYNC = false: the caller has a barrier of its own before s_w is written again.

@@ -125,6 +125,22 @@ def far():
     return [ivs]
 
 
+# batches of more lists than one pass of the offsets kernel takes: one pass exactly, one list into the second, one into the third
+MANY_LISTS = (CHUNK, CHUNK + 1, 2 * CHUNK + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def many_lists(n):
+    """n lists, list l of l % 4 short disjoint entries (a segment each): counts of 0 to 3 on both sides of every pass
+    border of the exclusive sum over the lists.  Kept out of CASES: the tests that walk CASES need no batch of this size."""
+    return [_short_run(l % 4, first=100 + 7 * l) for l in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def many_lists_answers(n):
+    return R.flat(R.single(many_lists(n)))
+
+
 MIXED = {"mixed": mixed, "empty_between": empty_between}
 TARGETED = {"disjoint": disjoint, "duplicated": duplicated, "abutting": abutting, "equal_starts": equal_starts, "nested": nested,
             "carry_two_long": carry_two_long, "carry_one_long": carry_one_long, "last_slot_only": last_slot_only,

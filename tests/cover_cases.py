@@ -128,6 +128,28 @@ CASES = {"mixed": mixed, "nested": nested, "boundaries": boundaries, "contig_bor
          "empty_between": empty_between}
 
 
+GRID_Y = 65535  # the most lists one launch of a search kernel takes side by side: list l + GRID_Y is the same thread's next trip
+
+
+@functools.lru_cache(maxsize=None)
+def many_lists():
+    """GRID_Y + 2 lists of 0 to 2 entries and three queries: lists GRID_Y and GRID_Y + 1 are the second trip of the threads
+    that answered lists 0 and 1, and the two of each pair are built to answer differently.  Kept out of CASES: the tests
+    that walk CASES need no batch of this size."""
+    rng = random.Random(65537)
+    lists = [random_list(rng, rng.randrange(3), contigs=(0,), contig_len=10000, reach=0.4) for _ in range(GRID_Y + 2)]
+    lists[0] = [(R.key(0, 0), R.key(0, 10000))]
+    lists[1] = []
+    lists[GRID_Y] = []
+    lists[GRID_Y + 1] = [(R.key(0, 500), R.key(0, 2500)), (R.key(0, 4000), R.key(0, 9500))]
+    return lists, [(R.key(0, 5000), R.key(0, 5200)), (R.key(0, 1000), R.key(0, 2000)), (R.key(0, 100), R.key(0, 9000))]
+
+
+@functools.lru_cache(maxsize=None)
+def many_lists_answers():
+    return R.cover(*many_lists())
+
+
 @functools.lru_cache(maxsize=None)
 def answers(name):
     lists, queries = CASES[name]()

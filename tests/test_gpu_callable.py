@@ -47,6 +47,23 @@ def test_the_mixed_case_holds_the_edges_of_the_scan():
     assert K.CHUNK == 1024  # SVX_COVER_SCAN_CHUNK: 256 lanes of four slots
 
 
+@pytest.mark.parametrize("n", K.MANY_LISTS)
+def test_more_lists_than_one_pass_of_the_offsets(svx_ctx, n):
+    """seg_off over CHUNK, CHUNK + 1 and 2 * CHUNK + 1 lists: the exclusive sum of the lists' counts carries its running
+    count from one pass of CHUNK lists to the next.  By the restatement alone the count is above 0 at every pass border,
+    grows from border to border and the lists around a border are not all empty: a carry that is dropped shows."""
+    lists = K.many_lists(n)
+    K.check_inputs(lists)
+    lo, hi, off = K.many_lists_answers(n)
+    assert len(lists) == n and [len(ivs) for ivs in lists[K.CHUNK - 1:K.CHUNK + 2]] == [3, 0, 1][:n - K.CHUNK + 1]
+    assert sum(len(ivs) for ivs in lists) == len(lo) <= 3100
+    borders = list(range(K.CHUNK, n, K.CHUNK))
+    assert len(borders) == (n - 1) // K.CHUNK
+    for b in borders:
+        assert off[b] > off[b - K.CHUNK] and off[b - 1] < off[b]
+    assert on_device(svx_ctx, lists) == (lo, hi, off)
+
+
 def test_no_lists_and_lists_without_entries(svx_ctx):
     none = np.zeros(0, np.uint64)
     assert on_device(svx_ctx, []) == ([], [], [0])

@@ -58,6 +58,20 @@ def test_query_counts(svx_ctx, n_q):
     assert on_device(svx_ctx, lists, queries[:n_q]) == expected
 
 
+def test_more_lists_than_one_launch_takes_side_by_side(svx_ctx):
+    """GRID_Y + 2 lists: the threads of lists 0 and 1 answer lists GRID_Y and GRID_Y + 1 in a second trip.  Each pair
+    answers differently by the restatement, so a trip that is missing or that lands on the first one's row cannot pass."""
+    lists, queries = K.many_lists()
+    K.check_inputs(lists, queries)
+    expected = K.many_lists_answers()
+    assert len(lists) == K.GRID_Y + 2 == 65537 and len(queries) == 3 and max(len(ivs) for ivs in lists) == 2
+    assert expected[0] != expected[K.GRID_Y] and expected[1] != expected[K.GRID_Y + 1]
+    assert all(0 < sum(row[q] for row in expected) < len(lists) for q in range(3))
+    got = svx_ctx.cover_query(*arrays(lists, queries))
+    assert got.dtype == np.uint8 and got.shape == (len(lists), 3)
+    assert np.array_equal(got, np.array(expected, dtype=np.uint8))
+
+
 def test_queries_are_in_no_order():
     for name in K.CASES:
         los = [q[0] for q in K.CASES[name]()[1]]

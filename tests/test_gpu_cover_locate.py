@@ -49,6 +49,18 @@ def test_query_counts(svx_ctx, n_q):
     assert on_device(svx_ctx, lists, queries[:n_q]) == [row[:n_q] for row in located("mixed")]
 
 
+def test_more_lists_than_one_launch_takes_side_by_side(svx_ctx):
+    """tests/test_gpu_cover.py's batch of GRID_Y + 2 lists: the second trip of k_locate_search's threads."""
+    lists, queries = K.many_lists()
+    expected = LR.locate(lists, queries)
+    assert [[int(i != LR.NONE) for i in row] for row in expected] == K.many_lists_answers()
+    assert expected[0] != expected[K.GRID_Y] and expected[1] != expected[K.GRID_Y + 1]
+    assert {0, 1, LR.NONE} == set(i for row in expected for i in row)
+    got = svx_ctx.cover_locate(*arrays(lists, queries))
+    assert got.dtype == np.uint32 and got.shape == (len(lists), 3)
+    assert np.array_equal(got, np.array(expected, dtype=np.uint32))
+
+
 def equal_ends():
     """Runs of entries with one end key, spread over lanes, waves and passes: the lowest index of the run wins."""
     c = 3
