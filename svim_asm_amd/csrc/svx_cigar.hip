@@ -1729,17 +1729,37 @@ void k_finish_a3(CigarArgs p, A3Args a, uint32_t n_a3_blocks) {
 #endif
 }
 
-// Fills the chain's arguments from a plan; takes the tree's and the post-passes' scratch from the workspace
-// (reserved by the caller together with the CIGAR path's).
-void a3_fill(svx_ctx* ctx, const uint32_t* d_cigar, const uint64_t* d_aln_off, const svx_a3_plan& q, uint64_t post_stride,
+// The CIGAR path's workspace for a batch of n_ops ops, added to `ws`: the arrays of `a`, whose n_tiles it sets; returns
+// whether the batch takes the two-launch path.  (svx_cigar_extract_ws_need measures the same list.)
+bool cigar_ws_takes(svx_takes& ws, const svx_ctx* ctx, uint64_t n_ops, CigarArgs* a) {
+    const bool small = n_ops <= (uint64_t)kSmallMaxTiles * kSmallTileOps && n_ops <= ctx->small_batch_ops;
+    const uint32_t n_tiles = small ? (uint32_t)((n_ops + kSmallTileOps - 1) / kSmallTileOps)
+                                   : (uint32_t)((n_ops + kTileOps - 1) / kTileOps);
+    const uint32_t n_scan_blocks = (n_tiles + kScanBlock - 1) / kScanBlock;
+    a->n_tiles = n_tiles;
+    ws.add(&a->desc, n_tiles);
+    ws.add(&a->desc4, (n_tiles + kWaves - 1) / kWaves);
+    ws.add(&a->slab, (size_t)n_tiles * kSlab);
+    ws.add(&a->out_base, n_tiles);
+    ws.add(&a->carry_ref, n_tiles);
+    ws.add(&a->carry_read, n_tiles);
+    ws.add(&a->dense_list, n_tiles);
+    ws.add(&a->tile_alo, n_tiles);
+    ws.add(&a->blk_agg, n_scan_blocks);
+    ws.add(&a->blk_prefix, n_scan_blocks);
+    return small;
+}
+
+// Fills the chain's arguments from a plan; adds the tree's and the post-passes' scratch to the caller's workspace list
+// (behind the CIGAR path's; tree.seg_rl follows seg_rl once the list is laid out).
+void a3_fill(svx_takes& ws, const uint32_t* d_cigar, const uint64_t* d_aln_off, const svx_a3_plan& q, uint64_t post_stride,
              A3Args* a) {
     a->rows = SegRowArgs{d_cigar, d_aln_off, q.d_seg_src, q.d_seg_tid, q.d_seg_pos, q.d_seg_rev, q.d_seg_qend, q.n_segs,
                          q.d_read_off, q.n_reads, q.d_segs, q.d_read_len};
-    a->seg_rl = svx_ws_take<int32_t>(ctx, q.n_segs ? q.n_segs : 1);
+    ws.add(&a->seg_rl, q.n_segs ? q.n_segs : 1);
     a->tree.segs = q.d_segs;
-    a->tree.seg_rl = a->seg_rl;
     a->tree.read_len_out = q.d_read_len;
-    a->tree.sorted = svx_ws_take<svx_seg>(ctx, q.n_segs ? q.n_segs : 1);
+    ws.add(&a->tree.sorted, q.n_segs ? q.n_segs : 1);
     a->tree.read_off = q.d_read_off;
     a->tree.read_len = q.d_read_len;
     a->tree.n_reads = q.n_reads;
@@ -1749,7 +1769,7 @@ void a3_fill(svx_ctx* ctx, const uint32_t* d_cigar, const uint64_t* d_aln_off, c
     o.raw = q.d_raw; o.read_off = q.d_read_off; o.n_reads = q.n_reads; o.contig_rank = q.d_contig_rank; o.n_contigs = q.n_contigs;
     o.min_sv = q.params.min_sv_size; o.max_sv = q.params.max_sv_size;
     o.out = q.d_post; o.out_off = q.d_post_off; o.out_cnt = q.d_post_cnt;
-    o.scratch = svx_ws_take<char>(ctx, (size_t)q.n_reads * post_stride);
+    ws.add(&o.scratch, (size_t)q.n_reads * post_stride);
     o.scratch_off = nullptr;
     o.scratch_stride = post_stride;
     // reads per workgroup of the rows + tree stage when the caller hands over no table: one or two while the grid stays
@@ -1799,52 +1819,34 @@ int cigar_extract_dev_impl(svx_ctx* ctx, const uint32_t* d_cigar_or_len, const u
         SVX_SET_ERR(ctx, "device CIGAR buffers must be 16-byte aligned");
         return SVX_E_INVALID;
     }
-    const bool small = n_ops <= (uint64_t)kSmallMaxTiles * kSmallTileOps && n_ops <= ctx->small_batch_ops;
-    const uint32_t n_tiles = small ? (uint32_t)((n_ops + kSmallTileOps - 1) / kSmallTileOps)
-                                   : (uint32_t)((n_ops + kTileOps - 1) / kTileOps);
-    size_t need = svx_cigar_extract_ws_need(ctx, n_ops);
-    if (a3) need += svx_take_bytes(a3->n_segs ? a3->n_segs : 1, sizeof(svx_seg)) + svx_take_bytes(a3->n_segs ? a3->n_segs : 1, 4) +
-                    svx_take_bytes((size_t)a3->n_reads * a3->post_stride, 1);
-    int rc = svx_ws_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-
     CigarArgs a;
+    A3Args c;
+    memset(&c, 0, sizeof(c));
+    svx_takes ws;
+    const bool small = cigar_ws_takes(ws, ctx, n_ops, &a);
+    if (a3) a3_fill(ws, d_cigar_or_len, d_aln_off, *a3, a3->post_stride, &c);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    c.tree.seg_rl = c.seg_rl;
+    const uint32_t n_tiles = a.n_tiles, n_scan_blocks = (n_tiles + kScanBlock - 1) / kScanBlock;
     a.cigar = d_cigar_or_len;
     a.op = d_op;
     a.aln_off = d_aln_off;
     a.ref_start = d_ref_start;
     a.n_ops = n_ops;
     a.n_aln = n_aln;
-    a.n_tiles = n_tiles;
     a.min_len = min_len;
     a.n_dense = reinterpret_cast<uint32_t*>(ctx->ws);  // workspace header: zero at allocation, self-cleaning
-    a.desc = svx_ws_take<uint4>(ctx, n_tiles);
-    a.desc4 = svx_ws_take<uint4>(ctx, (n_tiles + kWaves - 1) / kWaves);
-    a.slab = svx_ws_take<uint4>(ctx, (size_t)n_tiles * kSlab);
-    a.out_base = svx_ws_take<uint32_t>(ctx, n_tiles);
-    a.carry_ref = svx_ws_take<uint32_t>(ctx, n_tiles);
-    a.carry_read = svx_ws_take<uint32_t>(ctx, n_tiles);
-    a.dense_list = svx_ws_take<uint32_t>(ctx, n_tiles);
-    a.tile_alo = svx_ws_take<uint32_t>(ctx, n_tiles);
-    const uint32_t n_scan_blocks = (n_tiles + kScanBlock - 1) / kScanBlock;
-    a.blk_agg = svx_ws_take<uint4>(ctx, n_scan_blocks);
-    a.blk_prefix = svx_ws_take<uint4>(ctx, n_scan_blocks);
     a.out = d_out;
     a.cap = cap;
-    A3Args c;
-    memset(&c, 0, sizeof(c));
     uint32_t n_a3_blocks = 0, n_post_blocks = 0;
     if (a3) {
-        a3_fill(ctx, d_cigar_or_len, d_aln_off, *a3, a3->post_stride, &c);
         n_a3_blocks = c.deal ? c.n_deal : (a3->n_reads + c.reads_per_block - 1) / c.reads_per_block;
         n_post_blocks = (a3->n_reads + 255u) / 256u;
     }
 
     if (small) {  // two launches: tiles of 1024 ops (+ the split-segment chain); scan + finish + dense tiles
-        rc = svx_timing_begin(ctx);
-        if (rc != SVX_OK) return rc;
-        rc = svx_timing_mark(ctx, 1);
-        if (rc != SVX_OK) return rc;
+        SVX_TRY(svx_timing_begin(ctx));
+        SVX_TRY(svx_timing_mark(ctx, 1));
         const uint32_t tile_blocks = (n_tiles + kWaves - 1) / kWaves;
         if (a3)
             hipLaunchKernelGGL((k_tiles_a3<SOA, kSmallTileOps, ALO_SEARCH>), dim3(n_a3_blocks + tile_blocks), dim3(64 * kWaves), 0,
@@ -1852,8 +1854,7 @@ int cigar_extract_dev_impl(svx_ctx* ctx, const uint32_t* d_cigar_or_len, const u
         else
             hipLaunchKernelGGL((k_cigar_tiles<SOA, kSmallTileOps, ALO_SEARCH>), dim3(tile_blocks), dim3(64 * kWaves), 0,
                                ctx->stream, a);
-        rc = svx_timing_mark(ctx, 2);
-        if (rc != SVX_OK) return rc;
+        SVX_TRY(svx_timing_mark(ctx, 2));
         if (ctx->want_dom) {
             if (!ctx->ev_dom) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dom, hipEventDisableTiming));
             SVX_HIP(ctx, hipEventRecord(ctx->ev_dom, ctx->stream));
@@ -1878,15 +1879,12 @@ int cigar_extract_dev_impl(svx_ctx* ctx, const uint32_t* d_cigar_or_len, const u
     const uint32_t blocks_cap = (uint32_t)ctx->n_cu * 8u;
     const uint32_t finish_blocks = (n_tiles + 256 / kFinLanes - 1) / (256 / kFinLanes);
     const uint32_t dense_blocks = n_tiles < blocks_cap ? n_tiles : blocks_cap;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
     hipLaunchKernelGGL(k_tile_alo, dim3((n_aln + 255) / 256), dim3(256), 0, ctx->stream, d_aln_off, n_aln, n_tiles,
                        a.tile_alo);
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL((k_cigar_tiles<SOA, kTileOps, ALO_TABLE>), dim3(blocks_all), dim3(64 * kWaves), 0, ctx->stream, a);
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     if (ctx->want_dom) {  // somebody pipelines against this context (svx_ctx_wait_dominant)
         if (!ctx->ev_dom) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dom, hipEventDisableTiming));
         SVX_HIP(ctx, hipEventRecord(ctx->ev_dom, ctx->stream));
@@ -1928,50 +1926,42 @@ int cigar_extract_host_impl(svx_ctx* ctx, const uint32_t* cigar_or_len, const ui
                             uint32_t min_len, svx_sig_soa out, uint64_t cap, uint64_t* n_out) {
     if (!ctx || !n_out) return SVX_E_INVALID;
     *n_out = 0;
-    int rc = validate_offsets(ctx, aln_off, n_aln);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(validate_offsets(ctx, aln_off, n_aln));
     const uint64_t n_ops = n_aln ? aln_off[n_aln] : 0;
     if (n_ops == 0) return SVX_OK;
     if (!cigar_or_len || (SOA && !op)) return SVX_E_INVALID;
     if (n_ops >= (1ull << 32)) return SVX_E_TOO_LARGE;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    size_t need = svx_take_bytes(n_ops, 4) + (SOA ? svx_take_bytes(n_ops, 1) : 0) +
-                  svx_take_bytes((size_t)n_aln + 1, 8) + svx_take_bytes(n_aln, 4) +
-                  4 * svx_take_bytes(cap, 4) + svx_take_bytes(cap, 1) + svx_take_bytes(1, 8);
-    rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    uint32_t* d_c = svx_stage_take<uint32_t>(ctx, n_ops);
-    uint8_t* d_op = SOA ? svx_stage_take<uint8_t>(ctx, n_ops) : nullptr;
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_aln + 1);
-    int32_t* d_rs = ref_start ? svx_stage_take<int32_t>(ctx, n_aln) : nullptr;
+    uint32_t* d_c;
+    uint8_t* d_op = nullptr;
+    uint64_t *d_off, *d_n;
+    int32_t* d_rs = nullptr;
     svx_sig_soa d_out;
-    d_out.aln = svx_stage_take<uint32_t>(ctx, cap);
-    d_out.ref_pos = svx_stage_take<uint32_t>(ctx, cap);
-    d_out.read_pos = svx_stage_take<uint32_t>(ctx, cap);
-    d_out.len = svx_stage_take<uint32_t>(ctx, cap);
-    d_out.type = svx_stage_take<uint8_t>(ctx, cap);
-    uint64_t* d_n = svx_stage_take<uint64_t>(ctx, 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d_c, cigar_or_len, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (SOA) SVX_HIP(ctx, hipMemcpyAsync(d_op, op, n_ops, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice,
-                                ctx->stream));
-    if (d_rs)
-        SVX_HIP(ctx, hipMemcpyAsync(d_rs, ref_start, (size_t)n_aln * 4, hipMemcpyHostToDevice,
-                                    ctx->stream));
-    rc = cigar_extract_dev_impl<SOA>(ctx, d_c, d_op, n_ops, d_off, n_aln, d_rs, min_len, d_out, cap,
-                                     d_n);
-    if (rc != SVX_OK) return rc;
+    svx_takes st;
+    st.add_up(&d_c, cigar_or_len, n_ops);
+    if (SOA) st.add_up(&d_op, op, n_ops);
+    st.add_up(&d_off, aln_off, (size_t)n_aln + 1);
+    if (ref_start) st.add_up(&d_rs, ref_start, n_aln);
+    st.add(&d_out.aln, cap);
+    st.add(&d_out.ref_pos, cap);
+    st.add(&d_out.read_pos, cap);
+    st.add(&d_out.len, cap);
+    st.add(&d_out.type, cap);
+    st.add(&d_n, 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(cigar_extract_dev_impl<SOA>(ctx, d_c, d_op, n_ops, d_off, n_aln, d_rs, min_len, d_out, cap,
+                                     d_n));
     uint64_t n = 0;
-    SVX_HIP(ctx, hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_download(ctx, &n, d_n, 1));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = n;
     const uint64_t m = n < cap ? n : cap;
     if (m) {
-        SVX_HIP(ctx, hipMemcpyAsync(out.aln, d_out.aln, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.ref_pos, d_out.ref_pos, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.read_pos, d_out.read_pos, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.len, d_out.len, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.type, d_out.type, m, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_TRY(svx_download(ctx, out.aln, d_out.aln, m));
+        SVX_TRY(svx_download(ctx, out.ref_pos, d_out.ref_pos, m));
+        SVX_TRY(svx_download(ctx, out.read_pos, d_out.read_pos, m));
+        SVX_TRY(svx_download(ctx, out.len, d_out.len, m));
+        SVX_TRY(svx_download(ctx, out.type, d_out.type, m));
         SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (n > cap) {
@@ -2039,47 +2029,38 @@ extern "C" int svx_cigar_stats_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64
 extern "C" int svx_cigar_stats(svx_ctx* ctx, const uint32_t* cigar, const uint64_t* aln_off,
                                uint32_t n_aln, svx_aln_stats out) {
     if (!ctx) return SVX_E_INVALID;
-    int rc = validate_offsets(ctx, aln_off, n_aln);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(validate_offsets(ctx, aln_off, n_aln));
     if (n_aln == 0) return SVX_OK;
     const uint64_t n_ops = aln_off[n_aln];
     if (n_ops && !cigar) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    size_t need = svx_take_bytes(n_ops, 4) + svx_take_bytes((size_t)n_aln + 1, 8) +
-                  5 * svx_take_bytes(n_aln, 4);
-    rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    uint32_t* d_c = svx_stage_take<uint32_t>(ctx, n_ops ? n_ops : 1);
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_aln + 1);
+    uint32_t* d_c;
+    uint64_t* d_off;
     svx_aln_stats d;
-    d.ref_len = svx_stage_take<uint32_t>(ctx, n_aln);
-    d.q_start = svx_stage_take<uint32_t>(ctx, n_aln);
-    d.q_end = svx_stage_take<uint32_t>(ctx, n_aln);
-    d.read_len = svx_stage_take<uint32_t>(ctx, n_aln);
-    d.n_hard = svx_stage_take<uint32_t>(ctx, n_aln);
-    if (n_ops) SVX_HIP(ctx, hipMemcpyAsync(d_c, cigar, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice,
-                                ctx->stream));
-    rc = svx_cigar_stats_dev(ctx, d_c, n_ops, d_off, n_aln, d);
-    if (rc != SVX_OK) return rc;
-    const size_t b = (size_t)n_aln * 4;
-    if (out.ref_len) SVX_HIP(ctx, hipMemcpyAsync(out.ref_len, d.ref_len, b, hipMemcpyDeviceToHost, ctx->stream));
-    if (out.q_start) SVX_HIP(ctx, hipMemcpyAsync(out.q_start, d.q_start, b, hipMemcpyDeviceToHost, ctx->stream));
-    if (out.q_end) SVX_HIP(ctx, hipMemcpyAsync(out.q_end, d.q_end, b, hipMemcpyDeviceToHost, ctx->stream));
-    if (out.read_len) SVX_HIP(ctx, hipMemcpyAsync(out.read_len, d.read_len, b, hipMemcpyDeviceToHost, ctx->stream));
-    if (out.n_hard) SVX_HIP(ctx, hipMemcpyAsync(out.n_hard, d.n_hard, b, hipMemcpyDeviceToHost, ctx->stream));
+    svx_takes st;
+    if (n_ops) st.add_up(&d_c, cigar, n_ops); else st.add(&d_c, 1);
+    st.add_up(&d_off, aln_off, (size_t)n_aln + 1);
+    st.add(&d.ref_len, n_aln);
+    st.add(&d.q_start, n_aln);
+    st.add(&d.q_end, n_aln);
+    st.add(&d.read_len, n_aln);
+    st.add(&d.n_hard, n_aln);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_cigar_stats_dev(ctx, d_c, n_ops, d_off, n_aln, d));
+    if (out.ref_len) SVX_TRY(svx_download(ctx, out.ref_len, d.ref_len, n_aln));
+    if (out.q_start) SVX_TRY(svx_download(ctx, out.q_start, d.q_start, n_aln));
+    if (out.q_end) SVX_TRY(svx_download(ctx, out.q_end, d.q_end, n_aln));
+    if (out.read_len) SVX_TRY(svx_download(ctx, out.read_len, d.read_len, n_aln));
+    if (out.n_hard) SVX_TRY(svx_download(ctx, out.n_hard, d.n_hard, n_aln));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }
 
 size_t svx_cigar_extract_ws_need(const svx_ctx* ctx, uint64_t n_ops) {
-    const bool small = n_ops <= (uint64_t)kSmallMaxTiles * kSmallTileOps && n_ops <= ctx->small_batch_ops;
-    const uint32_t n_tiles = small ? (uint32_t)((n_ops + kSmallTileOps - 1) / kSmallTileOps)
-                                   : (uint32_t)((n_ops + kTileOps - 1) / kTileOps);
-    return svx_take_bytes(n_tiles, sizeof(uint4)) + svx_take_bytes((n_tiles + kWaves - 1) / kWaves, sizeof(uint4)) +
-           svx_take_bytes((size_t)n_tiles * kSlab, sizeof(uint4)) +
-           5 * svx_take_bytes(n_tiles, sizeof(uint32_t)) + svx_take_bytes(4, sizeof(uint32_t)) +
-           2 * svx_take_bytes((n_tiles + kScanBlock - 1) / kScanBlock, sizeof(uint4));
+    CigarArgs a;
+    svx_takes ws;
+    cigar_ws_takes(ws, ctx, n_ops, &a);
+    return ws.bytes();
 }
 
 extern "C" int svx_segments_rows_dev(svx_ctx* ctx, const uint32_t* d_cigar, const uint64_t* d_aln_off,

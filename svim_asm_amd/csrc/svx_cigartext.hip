@@ -224,25 +224,36 @@ __global__ void __launch_bounds__(kThreads) k_emit(const uint8_t* __restrict__ t
 
 }  // namespace
 
-size_t svx_cigar_text_ws_need(uint64_t n_bytes, uint32_t n_rec) {
-    const uint64_t n_chunks = (n_bytes + kChunk - 1) / kChunk;
-    return svx_take_bytes(n_chunks + 1, 4) + svx_take_bytes(n_chunks + 1, 8) + 2 * svx_take_bytes((size_t)n_rec + 1, 8) +
-           svx_take_bytes((size_t)n_rec + 1, 4) + 256;
+// the parser's scratch: what the need-function measures, the SAM reader's launcher places in its own buffer and the context's
+// entry lays out in the workspace
+struct TextScratch {
+    uint64_t n_chunks;
+    uint32_t *chunk_cnt, *n_ops;
+    uint64_t *chunk_base, *rank;
+    unsigned long long* err_key;
+};
+static void text_takes(svx_takes& t, uint64_t n_bytes, uint32_t n_rec, TextScratch* s) {
+    s->n_chunks = n_rec ? (n_bytes + kChunk - 1) / kChunk : 0;  // (text without records: nothing to parse)
+    t.add(&s->chunk_cnt, s->n_chunks + 1);
+    t.add(&s->chunk_base, s->n_chunks + 1);
+    t.add(&s->rank, (size_t)n_rec + 1);
+    t.add(&s->err_key, (size_t)n_rec + 1);
+    t.add(&s->n_ops, (size_t)n_rec + 1);
 }
 
-// The launches on `stream`; d_ws: svx_cigar_text_ws_need bytes, 256-byte aligned.  hipError_t as int.
-int svx_cigar_text_parse_on_stream(void* stream_, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
-                                   uint32_t* d_words, uint64_t cap, uint64_t* d_cigar_off, int32_t* d_ref_len, uint32_t* d_status,
-                                   void* d_ws) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const uint64_t n_chunks = n_rec ? (n_bytes + kChunk - 1) / kChunk : 0;  // (text without records: nothing to parse)
-    char* at = static_cast<char*>(d_ws);
-    auto take = [&](size_t count, size_t elem) { char* p = at; at += svx_align_up(count * elem, 256); return p; };
-    uint32_t* chunk_cnt = reinterpret_cast<uint32_t*>(take(n_chunks + 1, 4));
-    uint64_t* chunk_base = reinterpret_cast<uint64_t*>(take(n_chunks + 1, 8));
-    uint64_t* rank = reinterpret_cast<uint64_t*>(take((size_t)n_rec + 1, 8));
-    unsigned long long* err_key = reinterpret_cast<unsigned long long*>(take((size_t)n_rec + 1, 8));
-    uint32_t* n_ops = reinterpret_cast<uint32_t*>(take((size_t)n_rec + 1, 4));
+size_t svx_cigar_text_ws_need(uint64_t n_bytes, uint32_t n_rec) {
+    TextScratch s;
+    svx_takes t;
+    text_takes(t, n_bytes, n_rec, &s);
+    return t.bytes();
+}
+
+static int text_launch(hipStream_t stream, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
+                       uint32_t* d_words, uint64_t cap, uint64_t* d_cigar_off, int32_t* d_ref_len, uint32_t* d_status, const TextScratch& s) {
+    const uint64_t n_chunks = s.n_chunks;
+    uint32_t *chunk_cnt = s.chunk_cnt, *n_ops = s.n_ops;
+    uint64_t *chunk_base = s.chunk_base, *rank = s.rank;
+    unsigned long long* err_key = s.err_key;
     hipError_t e = hipMemsetAsync(err_key, 0xFF, ((size_t)n_rec + 1) * 8, stream);
     if (e == hipSuccess && n_rec) e = hipMemsetAsync(d_ref_len, 0, (size_t)n_rec * 4, stream);
     if (e != hipSuccess) return (int)e;
@@ -253,6 +264,17 @@ int svx_cigar_text_parse_on_stream(void* stream_, const uint8_t* d_text, uint64_
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanThreads), 0, stream, n_ops, (uint64_t)n_rec, d_cigar_off);
     if (n_chunks && n_rec) hipLaunchKernelGGL(k_emit, dim3((uint32_t)n_chunks), dim3(kThreads), 0, stream, d_text, n_bytes, d_rec_off, n_rec, chunk_base, rank, d_status, d_cigar_off, cap, d_words, d_ref_len);
     return (int)hipGetLastError();
+}
+
+// The launches on `stream`; d_ws: svx_cigar_text_ws_need bytes, 256-byte aligned.  hipError_t as int.
+int svx_cigar_text_parse_on_stream(void* stream, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
+                                   uint32_t* d_words, uint64_t cap, uint64_t* d_cigar_off, int32_t* d_ref_len, uint32_t* d_status,
+                                   void* d_ws) {
+    TextScratch s;
+    svx_takes t;
+    text_takes(t, n_bytes, n_rec, &s);
+    t.place(static_cast<char*>(d_ws), 0);
+    return text_launch(static_cast<hipStream_t>(stream), d_text, n_bytes, d_rec_off, n_rec, d_words, cap, d_cigar_off, d_ref_len, d_status, s);
 }
 
 extern "C" void svx_sam_register_device_parser(svx_cigar_text_launch_fn, svx_cigar_text_ws_fn);
@@ -270,21 +292,17 @@ extern "C" int svx_cigar_text_parse_dev(svx_ctx* ctx, const uint8_t* d_text, uin
         return SVX_E_INVALID;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t need = svx_cigar_text_ws_need(n_bytes, n_rec);
-    int rc = svx_ws_reserve(ctx, need + 256);
-    if (rc != SVX_OK) return rc;
-    char* ws = svx_ws_take<char>(ctx, need);
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    const int e = svx_cigar_text_parse_on_stream(ctx->stream, d_text, n_bytes, d_rec_off, n_rec, d_words, cap, d_cigar_off, d_ref_len,
-                                                 d_status, ws);
+    TextScratch s;
+    svx_takes ws;
+    text_takes(ws, n_bytes, n_rec, &s);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
+    const int e = text_launch(ctx->stream, d_text, n_bytes, d_rec_off, n_rec, d_words, cap, d_cigar_off, d_ref_len, d_status, s);
     if (e != 0) {
         SVX_SET_ERR(ctx, "svx_cigar_text_parse_dev: launch failed: %s", hipGetErrorString((hipError_t)e));
         return SVX_E_HIP;
     }
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     return svx_timing_end(ctx);
 }

@@ -71,8 +71,7 @@ extern "C" int svx_collect_batch_dev(svx_ctx* ctx, const svx_collect_dev* d) {
     if (d->n_chain_blocks && (!d->d_chain_deal || d->n_chain_blocks > d->n_reads || (reinterpret_cast<uintptr_t>(d->d_chain_deal) & 7u)))
         return SVX_E_INVALID;
     uint64_t stride = 0;
-    int rc = svx_postpass_plan(ctx, d->read_off, d->n_reads, d->post_off, &stride);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_postpass_plan(ctx, d->read_off, d->n_reads, d->post_off, &stride));
     if (d->post_off[d->n_reads] && !d->d_post) return SVX_E_INVALID;
     if (stride && !ctx->split_chain && d->n_ops != 0) {  // (records without a single op: nothing for the chain to ride in)
         // the chain goes out with the CIGAR path, inside two of its launches (svx_cigar.hip, a3_chain_block)
@@ -87,14 +86,11 @@ extern "C" int svx_collect_batch_dev(svx_ctx* ctx, const svx_collect_dev* d) {
                                            d->d_sig, d->sig_cap, d->d_n_sig, &q);
     }
     // reads too uneven for one scratch slice size (or svx_ctx_set_split_chain): the single-purpose launches
-    rc = svx_cigar_extract_dev(ctx, d->d_cigar, d->n_ops, d->d_aln_off, d->n_aln, d->d_ref_start, d->min_len, d->d_sig,
-                               d->sig_cap, d->d_n_sig);
-    if (rc != SVX_OK) return rc;
-    rc = svx_segments_rows_dev(ctx, d->d_cigar, d->d_aln_off, d->d_seg_src, d->d_seg_tid, d->d_seg_pos, d->d_seg_rev,
-                               d->d_seg_qend, d->n_segs, d->d_read_off, d->n_reads, d->d_segs, d->d_read_len);
-    if (rc != SVX_OK) return rc;
-    rc = svx_segments_classify_dev(ctx, d->d_segs, d->n_segs, d->d_read_off, d->n_reads, d->d_read_len, &d->params, d->d_raw);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_cigar_extract_dev(ctx, d->d_cigar, d->n_ops, d->d_aln_off, d->n_aln, d->d_ref_start, d->min_len, d->d_sig,
+                               d->sig_cap, d->d_n_sig));
+    SVX_TRY(svx_segments_rows_dev(ctx, d->d_cigar, d->d_aln_off, d->d_seg_src, d->d_seg_tid, d->d_seg_pos, d->d_seg_rev,
+                               d->d_seg_qend, d->n_segs, d->d_read_off, d->n_reads, d->d_segs, d->d_read_len));
+    SVX_TRY(svx_segments_classify_dev(ctx, d->d_segs, d->n_segs, d->d_read_off, d->n_reads, d->d_read_len, &d->params, d->d_raw));
     return svx_segments_postpass_dev(ctx, d->d_raw, d->read_off, d->d_read_off, d->n_reads, d->d_contig_rank, d->n_contigs,
                                      &d->params, d->d_post, d->post_off, d->d_post_off, d->d_post_cnt);
 }
@@ -231,17 +227,18 @@ extern "C" int svx_collect_batch(svx_ctx* ctx, const svx_collect_in* in, svx_col
     const size_t r_aln = rb.take(cap * 4), r_ref = rb.take(cap * 4), r_read = rb.take(cap * 4), r_len = rb.take(cap * 4);
     const size_t r_type = rb.take(cap), r_raw = rb.take((size_t)n_segs * sizeof(svx_raw)), r_post = rb.take(n_post * sizeof(svx_post));
     const size_t rb_bytes = rb.at;
-    int rc = host_stage_reserve(ctx, std::max(cb_bytes, rb_bytes));
-    if (rc != SVX_OK) return rc;
-    const size_t need = svx_take_bytes(n_ops + n_xops + 4, 4) + svx_take_bytes(cb_bytes, 1) + svx_take_bytes(rb_bytes, 1) +
-                        svx_take_bytes(n_segs ? n_segs : 1, sizeof(svx_seg)) + svx_take_bytes(n_reads ? n_reads : 1, 4);
-    rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    uint32_t* d_cigar = svx_stage_take<uint32_t>(ctx, n_ops + n_xops + 4);
-    char* d_cb = svx_stage_take<char>(ctx, cb_bytes);
-    char* d_rb = svx_stage_take<char>(ctx, rb_bytes);
-    svx_seg* d_segs = svx_stage_take<svx_seg>(ctx, n_segs ? n_segs : 1);
-    int32_t* d_read_len = svx_stage_take<int32_t>(ctx, n_reads ? n_reads : 1);
+    SVX_TRY(host_stage_reserve(ctx, std::max(cb_bytes, rb_bytes)));
+    uint32_t* d_cigar;
+    char *d_cb, *d_rb;
+    svx_seg* d_segs;
+    int32_t* d_read_len;
+    svx_takes st;
+    st.add(&d_cigar, n_ops + n_xops + 4);
+    st.add(&d_cb, cb_bytes);
+    st.add(&d_rb, rb_bytes);
+    st.add(&d_segs, n_segs ? n_segs : 1);
+    st.add(&d_read_len, n_reads ? n_reads : 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
 
     char* h = ctx->hpin;
     uint64_t* h_off = reinterpret_cast<uint64_t*>(h + o_off);
@@ -272,12 +269,12 @@ extern "C" int svx_collect_batch(svx_ctx* ctx, const svx_collect_in* in, svx_col
                 SVX_HIP(ctx, hipStreamWaitEvent(ctx->stream, static_cast<hipEvent_t>(in->part_ready[k]), 0));
             SVX_HIP(ctx, hipMemcpyAsync(d_cigar + at, in->part_dev[k], (size_t)in->part_ops[k] * 4, hipMemcpyDeviceToDevice, ctx->stream));
         } else if (in->part_ops[k]) {
-            SVX_HIP(ctx, hipMemcpyAsync(d_cigar + at, in->cigar_parts[k], (size_t)in->part_ops[k] * 4, hipMemcpyHostToDevice, ctx->stream));
+            SVX_TRY(svx_upload(ctx, d_cigar + at, in->cigar_parts[k], in->part_ops[k]));
         }
         at += in->part_ops[k];
     }
-    if (n_xops) SVX_HIP(ctx, hipMemcpyAsync(d_cigar + n_ops, in->extra_cigar, (size_t)n_xops * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_cb, h, cb_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SVX_TRY(svx_upload(ctx, d_cigar + n_ops, in->extra_cigar, n_xops));
+    SVX_TRY(svx_upload(ctx, d_cb, h, cb_bytes));
 
     // ---- kernels (svx_collect_batch_dev)
     svx_collect_dev dv;
@@ -297,14 +294,12 @@ extern "C" int svx_collect_batch(svx_ctx* ctx, const svx_collect_in* in, svx_col
     dv.d_post = reinterpret_cast<svx_post*>(d_rb + r_post); dv.post_off = out->post_off;
     dv.d_post_off = reinterpret_cast<const uint64_t*>(d_cb + o_poff); dv.d_post_cnt = reinterpret_cast<uint32_t*>(d_rb + r_cnt);
     if (n_deal > 0) { dv.d_chain_deal = reinterpret_cast<const uint32_t*>(d_cb + o_deal); dv.n_chain_blocks = (uint32_t)n_deal; }
-    rc = svx_collect_batch_dev(ctx, &dv);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_collect_batch_dev(ctx, &dv));
 
     // ---- read-back 1: the counts
-    SVX_HIP(ctx, hipMemcpyAsync(h, d_rb, head_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_download(ctx, h, d_rb, head_bytes));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = svx_barrier_check(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_barrier_check(ctx));
     const uint64_t n_sig = *reinterpret_cast<const uint64_t*>(h + r_n);
     out->n_sig = n_sig;
     if (n_reads) memcpy(out->post_cnt, h + r_cnt, (size_t)n_reads * 4);
@@ -316,7 +311,7 @@ extern "C" int svx_collect_batch(svx_ctx* ctx, const svx_collect_in* in, svx_col
     // (the columns sit at capacity strides; the gaps travel along when the capacity is generous, so the caller
     // sizes it from the op count)
     if (n_sig || n_segs || n_post) {
-        SVX_HIP(ctx, hipMemcpyAsync(h + r_aln, d_rb + r_aln, rb_bytes - r_aln, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_TRY(svx_download(ctx, h + r_aln, d_rb + r_aln, rb_bytes - r_aln));
         SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(out->sig.aln, h + r_aln, n_sig * 4);
         memcpy(out->sig.ref_pos, h + r_ref, n_sig * 4);

@@ -231,8 +231,7 @@ int check_lists(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
 int check_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off,
                 uint32_t n_lists, const uint64_t* q_lo, const uint64_t* q_hi, uint32_t n_q, const void* out) {
     if (!list_off || !q_lo || !q_hi || !out) return SVX_E_INVALID;
-    const int rc = check_lists(ctx, who, start_key, end_key, list_off, n_lists, false);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(check_lists(ctx, who, start_key, end_key, list_off, n_lists, false));
     for (uint32_t q = 0; q < n_q; ++q) {
         if ((q_lo[q] >> 32) != (q_hi[q] >> 32)) {
             SVX_SET_ERR(ctx, "%s: query %u starts and ends on different contigs", who, q);
@@ -246,21 +245,15 @@ int check_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
     return SVX_OK;
 }
 
-// the lists of a batch in the stage: what all three entries upload (lists_bytes of the caller's reserve)
+// the lists of a batch in the stage: what all three entries upload
 struct DevLists {
     uint64_t *start, *end, *off;
 };
-size_t lists_bytes(uint64_t n, uint32_t n_lists) { return 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8); }
-int upload_lists(svx_ctx* ctx, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off, uint32_t n_lists,
-                 DevLists* d) {
+void add_lists(svx_takes& st, const uint64_t* start_key, const uint64_t* end_key, const uint64_t* list_off, uint32_t n_lists, DevLists* d) {
     const uint64_t n = list_off[n_lists];
-    d->start = svx_stage_take<uint64_t>(ctx, n);
-    d->end = svx_stage_take<uint64_t>(ctx, n);
-    d->off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d->start, start_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d->end, end_key, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d->off, list_off, ((size_t)n_lists + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    return SVX_OK;
+    st.add_up(&d->start, start_key, n);
+    st.add_up(&d->end, end_key, n);
+    st.add_up(&d->off, list_off, (size_t)n_lists + 1);
 }
 
 // svx_cover_query (one byte per answer, prefix maxima alone in the workspace) and svx_cover_locate (`locate`: four bytes
@@ -271,8 +264,7 @@ int cover_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
                 int fill) {
     if (!ctx) return SVX_E_INVALID;
     if (n_lists == 0 || n_q == 0) return SVX_OK;
-    int rc = check_batch(ctx, who, start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(check_batch(ctx, who, start_key, end_key, list_off, n_lists, q_lo, q_hi, n_q, out));
     const uint64_t n = list_off[n_lists];
     for (uint32_t l = 0; l < n_lists; ++l)
         if (list_off[l + 1] - list_off[l] > list_limit) {
@@ -285,29 +277,26 @@ int cover_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
         return SVX_OK;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, lists_bytes(n, n_lists) + 2 * svx_take_bytes(n_q, 8) + svx_take_bytes(n_out, out_elem));
-    if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, svx_take_bytes(n, 8) + (locate ? svx_take_bytes(n, 4) : 0));
-    if (rc != SVX_OK) return rc;
     DevLists d;
-    rc = upload_lists(ctx, start_key, end_key, list_off, n_lists, &d);
-    if (rc != SVX_OK) return rc;
-    uint64_t* d_lo = svx_stage_take<uint64_t>(ctx, n_q);
-    uint64_t* d_hi = svx_stage_take<uint64_t>(ctx, n_q);
-    uint8_t* d_out = svx_stage_take<uint8_t>(ctx, n_out * out_elem);
-    uint64_t* d_max = svx_ws_take<uint64_t>(ctx, n);
-    uint32_t* d_idx = locate ? svx_ws_take<uint32_t>(ctx, n) : nullptr;
-    SVX_HIP(ctx, hipMemcpyAsync(d_lo, q_lo, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_hi, q_hi, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    uint64_t *d_lo, *d_hi, *d_max;
+    uint8_t* d_out;
+    uint32_t* d_idx = nullptr;
+    svx_takes st, ws;
+    add_lists(st, start_key, end_key, list_off, n_lists, &d);
+    st.add_up(&d_lo, q_lo, n_q);
+    st.add_up(&d_hi, q_hi, n_q);
+    st.add(&d_out, n_out * out_elem);
+    ws.add(&d_max, n);
+    if (locate) ws.add(&d_idx, n);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
     if (locate)
         hipLaunchKernelGGL(k_locate_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.end, d.off, d_max, d_idx);
     else
         hipLaunchKernelGGL(k_cover_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.end, d.off, d_max);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 1));
     const dim3 grid((n_q + kThreads - 1) / kThreads, n_lists < kMaxGridY ? n_lists : kMaxGridY);
     if (locate)
         hipLaunchKernelGGL(k_locate_search, grid, dim3(kThreads), 0, ctx->stream, d.start, d_max, d_idx, d.off, n_lists, d_lo, d_hi, n_q,
@@ -315,11 +304,9 @@ int cover_batch(svx_ctx* ctx, const char* who, const uint64_t* start_key, const 
     else
         hipLaunchKernelGGL(k_cover_search, grid, dim3(kThreads), 0, ctx->stream, d.start, d_max, d.off, n_lists, d_lo, d_hi, n_q, d_out);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(out, d_out, n_out * out_elem, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    SVX_TRY(svx_timing_end(ctx));
+    SVX_TRY(svx_download(ctx, static_cast<uint8_t*>(out), d_out, n_out * out_elem));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }
@@ -343,8 +330,7 @@ extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const u
     seg_off[0] = 0;
     if (n_lists == 0) return SVX_OK;
     if (!list_off) return SVX_E_INVALID;
-    int rc = check_lists(ctx, "svx_cover_single", start_key, end_key, list_off, n_lists, true);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(check_lists(ctx, "svx_cover_single", start_key, end_key, list_off, n_lists, true));
     const uint64_t n = list_off[n_lists];
     if (n == 0) {  // empty lists only
         memset(seg_off, 0, ((size_t)n_lists + 1) * 8);
@@ -356,36 +342,31 @@ extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const u
         return SVX_E_TOO_LARGE;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, lists_bytes(n, n_lists) + 2 * svx_take_bytes(n, 8) + svx_take_bytes((size_t)n_lists + 1, 8));
-    if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, 2 * svx_take_bytes(n, 8) + svx_take_bytes(n_lists, 8));
-    if (rc != SVX_OK) return rc;
     DevLists d;
-    rc = upload_lists(ctx, start_key, end_key, list_off, n_lists, &d);
-    if (rc != SVX_OK) return rc;
-    uint64_t* d_seg_lo = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_seg_hi = svx_stage_take<uint64_t>(ctx, n);
-    uint64_t* d_seg_off = svx_stage_take<uint64_t>(ctx, (size_t)n_lists + 1);
-    uint64_t* d_loc_lo = svx_ws_take<uint64_t>(ctx, n);
-    uint64_t* d_loc_hi = svx_ws_take<uint64_t>(ctx, n);
-    uint64_t* d_count = svx_ws_take<uint64_t>(ctx, n_lists);
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    uint64_t *d_seg_lo, *d_seg_hi, *d_seg_off, *d_loc_lo, *d_loc_hi, *d_count;
+    svx_takes st, ws;
+    add_lists(st, start_key, end_key, list_off, n_lists, &d);
+    st.add(&d_seg_lo, n);
+    st.add(&d_seg_hi, n);
+    st.add(&d_seg_off, (size_t)n_lists + 1);
+    ws.add(&d_loc_lo, n);
+    ws.add(&d_loc_hi, n);
+    ws.add(&d_count, n_lists);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL(k_single_scan, dim3(n_lists), dim3(kThreads), 0, ctx->stream, d.start, d.end, d.off, d_loc_lo, d_loc_hi, d_count);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     hipLaunchKernelGGL(k_single_offsets, dim3(1), dim3(kThreads), 0, ctx->stream, d_count, n_lists, d_seg_off);
     SVX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_single_pack, dim3(n_lists, kPackGridY), dim3(kThreads), 0, ctx->stream, d.off, d_seg_off, d_loc_lo, d_loc_hi,
                        d_seg_lo, d_seg_hi);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_end(ctx));
     // the offsets first: they say how many segments there are to fetch
-    SVX_HIP(ctx, hipMemcpyAsync(seg_off, d_seg_off, ((size_t)n_lists + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_download(ctx, seg_off, d_seg_off, (size_t)n_lists + 1));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t n_seg = seg_off[n_lists];
     if (n_seg > n) {  // (cannot happen: at most one segment per slot)
@@ -393,8 +374,8 @@ extern "C" int svx_cover_single(svx_ctx* ctx, const uint64_t* start_key, const u
         return SVX_E_HIP;
     }
     if (n_seg) {
-        SVX_HIP(ctx, hipMemcpyAsync(seg_lo, d_seg_lo, n_seg * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(seg_hi, d_seg_hi, n_seg * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_TRY(svx_download(ctx, seg_lo, d_seg_lo, n_seg));
+        SVX_TRY(svx_download(ctx, seg_hi, d_seg_hi, n_seg));
         SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return SVX_OK;

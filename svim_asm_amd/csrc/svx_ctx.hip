@@ -120,8 +120,7 @@ int svx_ws_reserve(svx_ctx* ctx, size_t total) {
     if (ctx->barrier_pending && total + 4096 > ctx->ws_bytes) {  // the note would go away with the old buffer
         SVX_HIP(ctx, hipSetDevice(ctx->device));
         SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        int rc = svx_barrier_check(ctx);
-        if (rc != SVX_OK) return rc;
+        SVX_TRY(svx_barrier_check(ctx));
     }
     // the first 4 KiB of the workspace are a header of self-cleaning counters (zeroed at
     // allocation, left at zero by the kernels that use them); per-call scratch starts after it
@@ -313,9 +312,10 @@ __global__ __launch_bounds__(256) void k_hbm_read_probe(const probe_u32x4* __res
 extern "C" int svx_hbm_read_probe_dev(svx_ctx* ctx, const void* d_buf, size_t bytes, uint32_t reps, float* ms_per_pass) {
     if (!ctx || !d_buf || !ms_per_pass || bytes < 16 || reps == 0 || (reinterpret_cast<uintptr_t>(d_buf) & 15u)) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_ws_reserve(ctx, 256);
-    if (rc != SVX_OK) return rc;
-    uint32_t* d_out = svx_ws_take<uint32_t>(ctx, 4);
+    uint32_t* d_out;
+    svx_takes ws;
+    ws.add(&d_out, 4);
+    SVX_TRY(svx_ws_lay(ctx, ws));
     const size_t n = bytes / 16;
     const size_t blocks = (n + 1023) / 1024;
     const dim3 grid((unsigned)(blocks < 102400 ? blocks : 102400));

@@ -497,18 +497,18 @@ extern "C" int svx_bgzf_deflate_dev(svx_ctx* ctx, const uint8_t* d_in, uint64_t 
     SVX_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t slice = g_slice.load();
     const uint64_t per = n_blk < slice ? n_blk : slice;
-    int rc = svx_ws_reserve(ctx, svx_take_bytes(n_blk + 1, 8) + svx_take_bytes(per * kStride, 1) + svx_take_bytes(per * kBlk, 4));
-    if (rc != SVX_OK) return rc;
-    uint64_t* d_off = svx_ws_take<uint64_t>(ctx, n_blk + 1);
-    uint8_t* d_stage = svx_ws_take<uint8_t>(ctx, per * kStride);
-    uint32_t* d_tok = svx_ws_take<uint32_t>(ctx, per * kBlk);
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    uint64_t* d_off;
+    uint8_t* d_stage;
+    uint32_t* d_tok;
+    svx_takes ws;
+    ws.add(&d_off, n_blk + 1);
+    ws.add(&d_stage, per * kStride);
+    ws.add(&d_tok, per * kBlk);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     SVX_HIP(ctx, (hipError_t)deflate_on_stream(ctx->stream, d_in, n, d_out, d_member_len, d_off, d_total, d_stage, d_tok, slice));
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     return svx_timing_end(ctx);
 }
 
@@ -619,16 +619,16 @@ int compress_device(svx_ctx* ctx, const uint8_t* src, uint64_t n, uint8_t** out,
     const uint64_t n_blk = (n + kBlk - 1u) / kBlk;
     const uint64_t bound = svx_bgzf_deflate_bound(n);
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_stage_reserve(ctx, svx_take_bytes(n ? n : 1, 1) + svx_take_bytes(bound, 1) + svx_take_bytes(n_blk + 1, 4) +
-                                        svx_take_bytes(1, 8));
-    if (rc != SVX_OK) return rc;
-    uint8_t* d_in = svx_stage_take<uint8_t>(ctx, n ? n : 1);
-    uint8_t* d_out = svx_stage_take<uint8_t>(ctx, bound);
-    uint32_t* d_mlen = svx_stage_take<uint32_t>(ctx, n_blk + 1);
-    uint64_t* d_total = svx_stage_take<uint64_t>(ctx, 1);
-    if (n) SVX_HIP(ctx, hipMemcpyAsync(d_in, src, n, hipMemcpyHostToDevice, ctx->stream));
-    rc = svx_bgzf_deflate_dev(ctx, d_in, n, d_out, bound, d_mlen, d_total);
-    if (rc != SVX_OK) return rc;
+    uint8_t *d_in, *d_out;
+    uint32_t* d_mlen;
+    uint64_t* d_total;
+    svx_takes st;
+    if (n) st.add_up(&d_in, src, n); else st.add(&d_in, 1);
+    st.add(&d_out, bound);
+    st.add(&d_mlen, n_blk + 1);
+    st.add(&d_total, 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_bgzf_deflate_dev(ctx, d_in, n, d_out, bound, d_mlen, d_total));
     uint32_t* sizes = (uint32_t*)malloc(n_blk ? n_blk * 4 : 4);
     if (!sizes) return SVX_E_NOMEM;
     uint64_t total = 0;

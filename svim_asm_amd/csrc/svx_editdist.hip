@@ -638,47 +638,47 @@ static int ed_validate_and_plan(svx_ctx* ctx, uint64_t seq_bytes, const uint64_t
     return SVX_OK;
 }
 
-static size_t ed_stage_need(uint32_t n_pairs, const EdPlan& plan) {
-    return 3 * svx_take_bytes(n_pairs, 8) + 5 * svx_take_bytes(n_pairs, 4) +
-           svx_take_bytes(plan.total_stream ? plan.total_stream : 1, 8);
+// the stage arrays of ed_run: the caller adds them to its list behind its own and lays the stage out
+struct EdScratch {
+    uint64_t *d_ao, *d_bo, *d_so;
+    uint32_t *d_al, *d_bl, *d_ord, *d_band, *d_dist;
+    uint64_t* d_stream;
+};
+static void ed_takes(svx_takes& st, uint32_t n_pairs, const EdPlan& plan, EdScratch* s) {
+    st.add(&s->d_ao, n_pairs);
+    st.add(&s->d_bo, n_pairs);
+    st.add(&s->d_so, n_pairs);
+    st.add(&s->d_al, n_pairs);
+    st.add(&s->d_bl, n_pairs);
+    st.add(&s->d_ord, n_pairs);
+    st.add(&s->d_band, n_pairs);
+    st.add(&s->d_dist, n_pairs);
+    st.add(&s->d_stream, plan.total_stream ? plan.total_stream : 1);
 }
 
-// d_seq: the sequence pool in HBM (already uploaded / built on the context's stream); the stage region
-// must have been reserved with ed_stage_need() bytes still free
+// d_seq: the sequence pool in HBM (already uploaded / built on the context's stream); s: laid out from ed_takes()
 // k_of != nullptr: per-pair threshold (0xFFFFFFFF = exact) instead of the one k_max for all
 static int ed_run(svx_ctx* ctx, const uint8_t* d_seq, const uint64_t* a_off, const uint32_t* a_len,
                   const uint64_t* b_off, const uint32_t* b_len, uint32_t n_pairs, uint32_t k_max, uint32_t* dist,
-                  const EdPlan& plan, const uint32_t* k_of = nullptr) {
+                  const EdPlan& plan, const EdScratch& s, const uint32_t* k_of = nullptr) {
     auto kmax_of = [&](uint32_t i) { return k_of ? k_of[i] : k_max; };
     auto exact_of = [&](uint32_t i) { return kmax_of(i) == 0xFFFFFFFFu; };
     const std::vector<uint32_t>& order = plan.order;
-    int rc;
     EdArgs a;
-    uint64_t* d_ao = svx_stage_take<uint64_t>(ctx, n_pairs);
-    uint64_t* d_bo = svx_stage_take<uint64_t>(ctx, n_pairs);
-    uint64_t* d_so = svx_stage_take<uint64_t>(ctx, n_pairs);
-    uint32_t* d_al = svx_stage_take<uint32_t>(ctx, n_pairs);
-    uint32_t* d_bl = svx_stage_take<uint32_t>(ctx, n_pairs);
-    uint32_t* d_ord = svx_stage_take<uint32_t>(ctx, n_pairs);
-    uint32_t* d_band = svx_stage_take<uint32_t>(ctx, n_pairs);
-    uint32_t* d_dist = svx_stage_take<uint32_t>(ctx, n_pairs);
-    uint64_t* d_stream = svx_stage_take<uint64_t>(ctx, plan.total_stream ? plan.total_stream : 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d_ao, a_off, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_bo, b_off, (size_t)n_pairs * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_al, a_len, (size_t)n_pairs * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_bl, b_len, (size_t)n_pairs * 4, hipMemcpyHostToDevice, ctx->stream));
-    a.seq = d_seq; a.a_off = d_ao; a.a_len = d_al; a.b_off = d_bo; a.b_len = d_bl;
-    a.dist = d_dist;
-    a.stream = d_stream;
-    a.stream_off = d_so;
-    a.order = d_ord;
-    a.band = d_band;
+    SVX_TRY(svx_upload(ctx, s.d_ao, a_off, n_pairs));
+    SVX_TRY(svx_upload(ctx, s.d_bo, b_off, n_pairs));
+    SVX_TRY(svx_upload(ctx, s.d_al, a_len, n_pairs));
+    SVX_TRY(svx_upload(ctx, s.d_bl, b_len, n_pairs));
+    a.seq = d_seq; a.a_off = s.d_ao; a.a_len = s.d_al; a.b_off = s.d_bo; a.b_len = s.d_bl;
+    a.dist = s.d_dist;
+    a.stream = s.d_stream;
+    a.stream_off = s.d_so;
+    a.order = s.d_ord;
+    a.band = s.d_band;
     SVX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_edit_myers<256>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<256>()));
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     // band per pair: the threshold itself, or (exact request) 256 widened per pair below
     std::vector<uint32_t> band_of(n_pairs);
     for (uint32_t i = 0; i < n_pairs; ++i) band_of[i] = exact_of(i) ? 256u : kmax_of(i);
@@ -701,19 +701,19 @@ static int ed_run(svx_ctx* ctx, const uint8_t* d_seq, const uint64_t* a_off, con
             lst_band[w] = (uint32_t)c;
             lds_cap = std::max(lds_cap, (uint32_t)c);
         }
-        SVX_HIP(ctx, hipMemcpyAsync(d_ord, order.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(d_band, lst_band.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, ctx->stream));
+        SVX_TRY(svx_upload(ctx, s.d_ord, order.data(), n_pairs));
+        SVX_TRY(svx_upload(ctx, s.d_band, lst_band.data(), n_pairs));
         WfaArgs wa;
-        wa.seq = d_seq; wa.a_off = d_ao; wa.a_len = d_al; wa.b_off = d_bo; wa.b_len = d_bl;
-        wa.order = d_ord; wa.cap = d_band; wa.n = n_pairs; wa.dist = d_dist;
+        wa.seq = d_seq; wa.a_off = s.d_ao; wa.a_len = s.d_al; wa.b_off = s.d_bo; wa.b_len = s.d_bl;
+        wa.order = s.d_ord; wa.cap = s.d_band; wa.n = n_pairs; wa.dist = s.d_dist;
         const size_t lds = (size_t)2 * (2 * (size_t)lds_cap + 3) * sizeof(int32_t);
         if (lds > 32768)  // (the largest cap, 4096 edits, needs 65 560 bytes of dynamic LDS: above the default limit)
             SVX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_edit_wfa),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_edit_wfa, dim3(n_pairs), dim3(64), lds, ctx->stream, wa, lds_cap);
         SVX_HIP(ctx, hipGetLastError());
-        SVX_HIP(ctx, hipMemcpyAsync(dist, d_dist, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
-        { int wrc = svx_wait_blocking(ctx); if (wrc != SVX_OK) return wrc; }
+        SVX_TRY(svx_download(ctx, dist, s.d_dist, n_pairs));
+        SVX_TRY(svx_wait_blocking(ctx));
         todo.clear();
         for (uint32_t w = 0; w < n_pairs; ++w) {
             const uint32_t i = order[w];
@@ -723,7 +723,7 @@ static int ed_run(svx_ctx* ctx, const uint8_t* d_seq, const uint64_t* a_off, con
             todo.push_back(i);
         }
     }
-    // (pairs the rounds below do not visit keep what the wavefront pass wrote: d_dist holds it)
+    // (pairs the rounds below do not visit keep what the wavefront pass wrote: s.d_dist holds it)
     while (!todo.empty()) {
         // one round: fast instantiation over `todo`, then the 256-symbol one over what it rejected
         for (int pass = 0; pass < 2; ++pass) {
@@ -737,17 +737,17 @@ static int ed_run(svx_ctx* ctx, const uint8_t* d_seq, const uint64_t* a_off, con
                 at += ed_stream_words(a_len[lst[w2]], b_len[lst[w2]]);
                 lst_band[w2] = band_of[lst[w2]];
             }
-            SVX_HIP(ctx, hipMemcpyAsync(d_ord, lst.data(), lst.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            SVX_HIP(ctx, hipMemcpyAsync(d_so, lst_soff.data(), lst.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            SVX_HIP(ctx, hipMemcpyAsync(d_band, lst_band.data(), lst.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            SVX_TRY(svx_upload(ctx, s.d_ord, lst.data(), lst.size()));
+            SVX_TRY(svx_upload(ctx, s.d_so, lst_soff.data(), lst.size()));
+            SVX_TRY(svx_upload(ctx, s.d_band, lst_band.data(), lst.size()));
             a.n = (uint32_t)lst.size();
             if (pass == 0)
                 hipLaunchKernelGGL(k_edit_myers<16>, dim3(a.n), dim3(64), lds_bytes<16>(), ctx->stream, a);
             else
                 hipLaunchKernelGGL(k_edit_myers<256>, dim3(a.n), dim3(64), lds_bytes<256>(), ctx->stream, a);
             SVX_HIP(ctx, hipGetLastError());
-            SVX_HIP(ctx, hipMemcpyAsync(dist, d_dist, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
-            { int wrc = svx_wait_blocking(ctx); if (wrc != SVX_OK) return wrc; }
+            SVX_TRY(svx_download(ctx, dist, s.d_dist, n_pairs));
+            SVX_TRY(svx_wait_blocking(ctx));
             if (pass == 0) {
                 big.clear();
                 for (uint32_t i : todo)
@@ -774,10 +774,8 @@ static int ed_run(svx_ctx* ctx, const uint8_t* d_seq, const uint64_t* a_off, con
         todo = again;
         big.clear();
     }
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    SVX_TRY(svx_timing_end(ctx));
     for (uint32_t i = 0; i < n_pairs; ++i) {
         if (dist[i] & kUnproven) dist[i] = 0xFFFFFFFFu;          // only "> k_max" is known (threshold request)
         else if (!exact_of(i) && dist[i] > kmax_of(i)) dist[i] = 0xFFFFFFFFu;
@@ -795,14 +793,15 @@ extern "C" int svx_edit_distance_batch(svx_ctx* ctx, const uint8_t* seq, uint64_
     if (n_pairs == 0) return SVX_OK;
     if (!a_off || !a_len || !b_off || !b_len || !dist || (seq_bytes && !seq)) return SVX_E_INVALID;
     EdPlan plan;
-    int rc = ed_validate_and_plan(ctx, seq_bytes, a_off, a_len, b_off, b_len, n_pairs, &plan);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(ed_validate_and_plan(ctx, seq_bytes, a_off, a_len, b_off, b_len, n_pairs, &plan));
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, svx_take_bytes(seq_bytes ? seq_bytes : 1, 1) + ed_stage_need(n_pairs, plan));
-    if (rc != SVX_OK) return rc;
-    uint8_t* d_seq = svx_stage_take<uint8_t>(ctx, seq_bytes ? seq_bytes : 1);
-    if (seq_bytes) SVX_HIP(ctx, hipMemcpyAsync(d_seq, seq, seq_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return ed_run(ctx, d_seq, a_off, a_len, b_off, b_len, n_pairs, k_max, dist, plan);
+    uint8_t* d_seq;
+    EdScratch s;
+    svx_takes st;
+    if (seq_bytes) st.add_up(&d_seq, seq, seq_bytes); else st.add(&d_seq, 1);
+    ed_takes(st, n_pairs, plan, &s);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    return ed_run(ctx, d_seq, a_off, a_len, b_off, b_len, n_pairs, k_max, dist, plan, s);
 }
 
 // pool: host bytes staged to HBM by this call, or (d_pool_resident != nullptr) already there
@@ -837,28 +836,27 @@ static int hap_distance_impl(svx_ctx* ctx, const uint8_t* pool, const uint8_t* d
         total += len;
     }
     EdPlan plan;
-    int rc = ed_validate_and_plan(ctx, total, a_off.data(), a_len.data(), b_off.data(), b_len.data(), n_pairs, &plan);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(ed_validate_and_plan(ctx, total, a_off.data(), a_len.data(), b_off.data(), b_len.data(), n_pairs, &plan));
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, (resident ? 0 : svx_take_bytes(pool_bytes ? pool_bytes : 1, 1)) + svx_take_bytes((size_t)n_strings * 3, sizeof(svx_hap_piece)) +
-                                    svx_take_bytes(n_strings, 8) + svx_take_bytes(total ? total : 1, 1) + ed_stage_need(n_pairs, plan));
-    if (rc != SVX_OK) return rc;
     HapArgs h;
     const uint8_t* d_pool = d_pool_resident;
+    svx_hap_piece* d_pc;
+    uint64_t* d_soff;
+    uint8_t* d_str;
+    EdScratch s;
+    svx_takes st;
     if (!resident) {
-        uint8_t* staged = svx_stage_take<uint8_t>(ctx, pool_bytes ? pool_bytes : 1);
-        if (pool_bytes) SVX_HIP(ctx, hipMemcpyAsync(staged, pool, pool_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_pool = staged;
+        if (pool_bytes) st.add_up(&d_pool, pool, pool_bytes); else st.add(&d_pool, 1);
     }
-    svx_hap_piece* d_pc = svx_stage_take<svx_hap_piece>(ctx, (size_t)n_strings * 3);
-    uint64_t* d_soff = svx_stage_take<uint64_t>(ctx, n_strings);
-    uint8_t* d_str = svx_stage_take<uint8_t>(ctx, total ? total : 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d_pc, pieces, (size_t)n_strings * 3 * sizeof(svx_hap_piece), hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_soff, str_off.data(), (size_t)n_strings * 8, hipMemcpyHostToDevice, ctx->stream));
+    st.add_up(&d_pc, pieces, (size_t)n_strings * 3);
+    st.add_up(&d_soff, str_off.data(), n_strings);
+    st.add(&d_str, total ? total : 1);
+    ed_takes(st, n_pairs, plan, &s);
+    SVX_TRY(svx_stage_lay(ctx, st));
     h.pool = d_pool; h.pieces = d_pc; h.str_off = d_soff; h.out = d_str; h.n_strings = n_strings;
     hipLaunchKernelGGL(k_hap_build, dim3(n_strings), dim3(256), 0, ctx->stream, h);
     SVX_HIP(ctx, hipGetLastError());
-    return ed_run(ctx, d_str, a_off.data(), a_len.data(), b_off.data(), b_len.data(), n_pairs, k_max, dist, plan, k_of);
+    return ed_run(ctx, d_str, a_off.data(), a_len.data(), b_off.data(), b_len.data(), n_pairs, k_max, dist, plan, s, k_of);
 }
 
 extern "C" int svx_haplotype_distance_batch(svx_ctx* ctx, const uint8_t* pool, uint64_t pool_bytes,

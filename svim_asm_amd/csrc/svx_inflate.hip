@@ -1517,25 +1517,22 @@ extern "C" int svx_bgzf_inflate_dev(svx_ctx* ctx, const uint8_t* d_in, const uin
     if (n_members == 0) return SVX_OK;
     if (!d_in || !d_in_off || !d_in_len || !d_isize || !d_crc || !d_out || !d_out_off || !d_status) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
     // the two-pass forms' token lists: an arena for up to kArenaMembers members at a time out of the context's workspace
     // (175 KB a member: 8 bytes per 3 bytes of output at most); a smaller one when the device has no room for it
     const uint32_t arena_max = g_arena_members.load();
     uint32_t arena = n_members < arena_max ? n_members : arena_max;
     uint32_t* d_n_tok = nullptr;
-    void* d_tok = nullptr;
+    uint2* d_tok = nullptr;
     for (; arena; arena = arena > 512u ? arena / 2u : 0u) {
-        if (svx_ws_reserve(ctx, svx_take_bytes(n_members, 4) + svx_take_bytes((size_t)arena * kTokStride, 8)) != SVX_OK) continue;
-        d_n_tok = svx_ws_take<uint32_t>(ctx, n_members);
-        d_tok = svx_ws_take<uint2>(ctx, (size_t)arena * kTokStride);
-        break;
+        svx_takes ws;
+        ws.add(&d_n_tok, n_members);
+        ws.add(&d_tok, (size_t)arena * kTokStride);
+        if (svx_ws_lay(ctx, ws) == SVX_OK) break;  // (else nothing was placed: both stay null)
     }  // (no room at all: the one-launch kernel)
-    rc = svx_timing_mark(ctx, 1);  // (behind the reservation: a workspace that has to grow is not kernel time)
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 1));  // (behind the reservation: a workspace that has to grow is not kernel time)
     SVX_HIP(ctx, (hipError_t)svx_bgzf_inflate_on_stream(ctx->stream, d_in, d_in_off, d_in_len, d_isize, d_crc, n_members, d_out, d_out_off,
                                                         d_status, d_n_tok, d_tok, d_tok ? arena : 0u));
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     return svx_timing_end(ctx);
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "svx.h"
+#include "svx_takes.h"
 
 struct svx_ctx {
     int device = 0;
@@ -63,7 +64,12 @@ struct svx_ctx {
         }                                                                               \
     } while (0)
 
-static inline size_t svx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Evaluate an int-returning call and pass on anything but SVX_OK.
+#define SVX_TRY(expr)                     \
+    do {                                  \
+        const int rc__ = (expr);          \
+        if (rc__ != SVX_OK) return rc__;  \
+    } while (0)
 
 // Reserve `total` bytes of workspace for this call (may reallocate; synchronises the
 // stream first when it has to, so earlier kernels never lose their scratch).
@@ -108,20 +114,32 @@ int svx_cigar_extract_chain_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t 
                                 const int32_t* d_ref_start, uint32_t min_len, svx_sig_soa d_out, uint64_t cap,
                                 uint64_t* d_n_out, const svx_a3_plan* a3);
 
+// Lay out a call's scratch (svx_takes.h): reserve the list's bytes() in the region and give every slot its address; the
+// stage also enqueues the list's uploads, in list order.  A lay-out starts its region from the front, as a reserve always
+// did: what an earlier one placed there is given up (work already on the stream still finishes in front of the new use).
+static inline int svx_ws_lay(svx_ctx* ctx, const svx_takes& t) {
+    SVX_TRY(svx_ws_reserve(ctx, t.bytes()));
+    ctx->ws_used = t.place(ctx->ws, ctx->ws_used);
+    return SVX_OK;
+}
+static inline int svx_stage_lay(svx_ctx* ctx, const svx_takes& t) {
+    SVX_TRY(svx_stage_reserve(ctx, t.bytes()));
+    ctx->stage_used = t.place(ctx->stage, ctx->stage_used);
+    for (int i = 0; i < t.n; ++i)
+        if (t.up_bytes(i))
+            SVX_HIP(ctx, hipMemcpyAsync(*(void**)t.s[i].at, t.s[i].src, t.up_bytes(i), hipMemcpyHostToDevice, ctx->stream));
+    return SVX_OK;
+}
+// `count` elements up to / down from the device on the context's stream (no element: no copy)
 template <typename T>
-static inline T* svx_ws_take(svx_ctx* ctx, size_t count) {
-    size_t off = svx_align_up(ctx->ws_used, 256);
-    ctx->ws_used = off + count * sizeof(T);
-    return reinterpret_cast<T*>(ctx->ws + off);
+static inline int svx_upload(svx_ctx* ctx, T* d_dst, const T* src, size_t count) {
+    if (count) SVX_HIP(ctx, hipMemcpyAsync(d_dst, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return SVX_OK;
 }
 template <typename T>
-static inline T* svx_stage_take(svx_ctx* ctx, size_t count) {
-    size_t off = svx_align_up(ctx->stage_used, 256);
-    ctx->stage_used = off + count * sizeof(T);
-    return reinterpret_cast<T*>(ctx->stage + off);
-}
-static inline size_t svx_take_bytes(size_t count, size_t elem) {
-    return svx_align_up(count * elem, 256) + 256;
+static inline int svx_download(svx_ctx* ctx, T* dst, const T* d_src, size_t count) {
+    if (count) SVX_HIP(ctx, hipMemcpyAsync(dst, d_src, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return SVX_OK;
 }
 
 // svx_lift.hip, shared with svx_mismatch.hip: aln_off[0] == 0, non-decreasing offsets and *n_ops = aln_off[n_aln] inside the

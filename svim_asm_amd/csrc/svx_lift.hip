@@ -121,8 +121,7 @@ __global__ __launch_bounds__(kThreads) void k_lift_query(const uint32_t* __restr
 // the host-side refusals of both entries
 int check_lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d_pool, uint64_t pool_ops, const uint64_t* aln_off,
                uint32_t n_aln, const uint32_t* q_aln, uint32_t n_q, uint64_t* n_ops) {
-    const int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, n_ops);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, n_ops));
     for (uint32_t q = 0; q < n_q; ++q)
         if (q_aln[q] >= n_aln) {
             SVX_SET_ERR(ctx, "%s: query %u names alignment %u of %u", who, q, q_aln[q], n_aln);
@@ -139,8 +138,7 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
     if (n_q == 0) return SVX_OK;
     if (!aln_off || !q_aln || !q_ref || !out_query || !out_state || (n_aln && !ref_start)) return SVX_E_INVALID;
     uint64_t n_ops;
-    int rc = check_lift(ctx, who, cigar, d_pool, pool_ops, aln_off, n_aln, q_aln, n_q, &n_ops);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(check_lift(ctx, who, cigar, d_pool, pool_ops, aln_off, n_aln, q_aln, n_q, &n_ops));
     if (n_ops == 0) {  // alignments without ops only
         memset(out_query, 0, (size_t)n_q * 4);
         memset(out_state, SVX_LIFT_OUTSIDE, n_q);
@@ -152,46 +150,37 @@ int lift(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_t* d
         return SVX_E_TOO_LARGE;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, (d_pool ? 0 : svx_take_bytes(n_ops, 4)) + svx_take_bytes((size_t)n_aln + 1, 8) + svx_take_bytes(n_aln, 4) +
-                                        svx_take_bytes(n_q, 4) + svx_take_bytes(n_q, 8) + svx_take_bytes(n_q, 4) + svx_take_bytes(n_q, 1));
-    if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, 2 * svx_take_bytes(n_ops, 8) + 2 * svx_take_bytes(n_chunks, sizeof(Use)));
-    if (rc != SVX_OK) return rc;
     const uint32_t* d_cigar = d_pool;
-    if (!d_pool) {
-        uint32_t* up = svx_stage_take<uint32_t>(ctx, n_ops);
-        SVX_HIP(ctx, hipMemcpyAsync(up, cigar, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_cigar = up;
-    }
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_aln + 1);
-    int32_t* d_start = svx_stage_take<int32_t>(ctx, n_aln);
-    uint32_t* d_qaln = svx_stage_take<uint32_t>(ctx, n_q);
-    int64_t* d_qref = svx_stage_take<int64_t>(ctx, n_q);
-    uint32_t* d_query = svx_stage_take<uint32_t>(ctx, n_q);
-    uint8_t* d_state = svx_stage_take<uint8_t>(ctx, n_q);
-    uint64_t* d_pref = svx_ws_take<uint64_t>(ctx, n_ops);
-    uint64_t* d_pqry = svx_ws_take<uint64_t>(ctx, n_ops);
-    Use* d_sum = svx_ws_take<Use>(ctx, n_chunks);
-    Use* d_base = svx_ws_take<Use>(ctx, n_chunks);
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_start, ref_start, (size_t)n_aln * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_qaln, q_aln, (size_t)n_q * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_qref, q_ref, (size_t)n_q * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    rc = svx_lift_prefixes(ctx, d_cigar, n_ops, d_sum, d_base, d_pref, d_pqry);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    uint64_t *d_off, *d_pref, *d_pqry;
+    int32_t* d_start;
+    uint32_t *d_qaln, *d_query;
+    int64_t* d_qref;
+    uint8_t* d_state;
+    Use *d_sum, *d_base;
+    svx_takes st, ws;
+    if (!d_pool) st.add_up(&d_cigar, cigar, n_ops);
+    st.add_up(&d_off, aln_off, (size_t)n_aln + 1);
+    st.add_up(&d_start, ref_start, n_aln);
+    st.add_up(&d_qaln, q_aln, n_q);
+    st.add_up(&d_qref, q_ref, n_q);
+    st.add(&d_query, n_q);
+    st.add(&d_state, n_q);
+    ws.add(&d_pref, n_ops);
+    ws.add(&d_pqry, n_ops);
+    ws.add(&d_sum, n_chunks);
+    ws.add(&d_base, n_chunks);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
+    SVX_TRY(svx_lift_prefixes(ctx, d_cigar, n_ops, d_sum, d_base, d_pref, d_pqry));
+    SVX_TRY(svx_timing_mark(ctx, 2));
     hipLaunchKernelGGL(k_lift_query, dim3((n_q + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, d_cigar, d_off, d_start, d_pref,
                        d_pqry, d_qaln, d_qref, n_q, d_query, d_state);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(out_query, d_query, (size_t)n_q * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(out_state, d_state, n_q, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_timing_end(ctx));
+    SVX_TRY(svx_download(ctx, out_query, d_query, n_q));
+    SVX_TRY(svx_download(ctx, out_state, d_state, n_q));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }
@@ -223,8 +212,7 @@ int svx_lift_prefixes(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops, svx
     const uint32_t n_chunks = (uint32_t)((n_ops + SVX_LIFT_CHUNK - 1) / SVX_LIFT_CHUNK);
     hipLaunchKernelGGL(k_lift_sums, dim3(n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_sum);
     SVX_HIP(ctx, hipGetLastError());
-    int rc = svx_lift_exclusive(ctx, d_sum, n_chunks, d_base);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_lift_exclusive(ctx, d_sum, n_chunks, d_base));
     hipLaunchKernelGGL(k_lift_apply, dim3(n_chunks), dim3(kThreads), 0, ctx->stream, d_cigar, n_ops, d_base, d_pref, d_pqry);
     SVX_HIP(ctx, hipGetLastError());
     return SVX_OK;

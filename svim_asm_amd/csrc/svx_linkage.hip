@@ -348,10 +348,23 @@ int launch_all(svx_ctx* ctx, LinkArgs a, const LinkPlan& pl) {
         a.class_hi = kGroupClasses[c].hi;
         lo = kGroupClasses[c].hi + 1;
         if (!pl.class_max[c]) continue;
-        const int rc = kGroupClasses[c].threads == 64 ? launch_group<64>(ctx, a, pl.class_max[c]) : launch_group<256>(ctx, a, pl.class_max[c]);
-        if (rc != SVX_OK) return rc;
+        SVX_TRY(kGroupClasses[c].threads == 64 ? launch_group<64>(ctx, a, pl.class_max[c]) : launch_group<256>(ctx, a, pl.class_max[c]));
     }
     return SVX_OK;
+}
+
+// both entries behind their offsets: the timed launches over arrays in HBM (after svx_timing_begin)
+int cut_timed(svx_ctx* ctx, const double* d_dist, const uint32_t* d_n_members, const uint64_t* d_doff, const uint64_t* d_loff,
+              const uint64_t* d_soff, char* d_scratch, uint32_t n_parts, double cutoff, uint32_t* d_labels, uint32_t group_min,
+              const LinkPlan& pl) {
+    LinkArgs a;
+    a.dist = d_dist; a.dist_off = d_doff; a.n_members = d_n_members; a.label_off = d_loff; a.scratch_off = d_soff;
+    a.scratch = d_scratch; a.n_parts = n_parts; a.cutoff = cutoff; a.labels = d_labels;
+    a.group_min = group_min; a.class_lo = a.class_hi = 0;
+    SVX_TRY(svx_timing_mark(ctx, 1));
+    SVX_TRY(launch_all(ctx, a, pl));
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    return svx_timing_end(ctx);
 }
 
 }  // namespace
@@ -374,26 +387,17 @@ extern "C" int svx_linkage_cut_batch_dev(svx_ctx* ctx, const double* d_dist, con
     if (n_dist && !d_dist) return SVX_E_INVALID;
     if (n_lab == 0) return SVX_OK;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_ws_reserve(ctx, 3 * svx_take_bytes(n_parts, 8) + svx_take_bytes(n_scratch ? n_scratch : 1, 1));
-    if (rc != SVX_OK) return rc;
-    LinkArgs a;
-    uint64_t* d_doff = svx_ws_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_loff = svx_ws_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_soff = svx_ws_take<uint64_t>(ctx, n_parts);
-    char* d_scratch = svx_ws_take<char>(ctx, n_scratch ? n_scratch : 1);
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    uint64_t *d_doff, *d_loff, *d_soff;
+    char* d_scratch;
+    svx_takes ws;
+    ws.add(&d_doff, n_parts);
+    ws.add(&d_loff, n_parts);
+    ws.add(&d_soff, n_parts);
+    ws.add(&d_scratch, n_scratch ? n_scratch : 1);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
     hipLaunchKernelGGL(k_linkage_offsets, dim3(1), dim3(256), 0, ctx->stream, d_n_members, n_parts, group_min, d_doff, d_loff, d_soff);
-    a.dist = d_dist; a.dist_off = d_doff; a.n_members = d_n_members; a.label_off = d_loff; a.scratch_off = d_soff;
-    a.scratch = d_scratch; a.n_parts = n_parts; a.cutoff = cutoff; a.labels = d_labels;
-    a.group_min = group_min; a.class_lo = a.class_hi = 0;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    rc = launch_all(ctx, a, pl);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    return svx_timing_end(ctx);
+    return cut_timed(ctx, d_dist, d_n_members, d_doff, d_loff, d_soff, d_scratch, n_parts, cutoff, d_labels, group_min, pl);
 }
 
 extern "C" int svx_linkage_cut_batch(svx_ctx* ctx, const double* dist, const uint32_t* n_members, uint32_t n_parts,
@@ -414,37 +418,22 @@ extern "C" int svx_linkage_cut_batch(svx_ctx* ctx, const double* dist, const uin
     if (n_dist && !dist) return SVX_E_INVALID;
     if (n_lab == 0) return SVX_OK;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    size_t need = svx_take_bytes(n_dist ? n_dist : 1, 8) + 3 * svx_take_bytes(n_parts, 8) + svx_take_bytes(n_parts, 4) +
-                  svx_take_bytes(n_lab, 4) + svx_take_bytes(n_scratch ? n_scratch : 1, 1);
-    int rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    LinkArgs a;
-    double* d_dist = svx_stage_take<double>(ctx, n_dist ? n_dist : 1);
-    uint64_t* d_doff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_loff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_soff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint32_t* d_nm = svx_stage_take<uint32_t>(ctx, n_parts);
-    uint32_t* d_lab = svx_stage_take<uint32_t>(ctx, n_lab);
-    char* d_scratch = svx_stage_take<char>(ctx, n_scratch ? n_scratch : 1);
-    if (n_dist) SVX_HIP(ctx, hipMemcpyAsync(d_dist, dist, n_dist * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_doff, dist_off.data(), (size_t)n_parts * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_loff, label_off.data(), (size_t)n_parts * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_soff, scratch_off.data(), (size_t)n_parts * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_nm, n_members, (size_t)n_parts * 4, hipMemcpyHostToDevice, ctx->stream));
-    a.dist = d_dist; a.dist_off = d_doff; a.n_members = d_nm; a.label_off = d_loff; a.scratch_off = d_soff;
-    a.scratch = d_scratch; a.n_parts = n_parts; a.cutoff = cutoff; a.labels = d_lab;
-    a.group_min = group_min; a.class_lo = a.class_hi = 0;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    rc = launch_all(ctx, a, pl);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(labels, d_lab, n_lab * 4, hipMemcpyDeviceToHost, ctx->stream));
+    double* d_dist;
+    uint64_t *d_doff, *d_loff, *d_soff;
+    uint32_t *d_nm, *d_lab;
+    char* d_scratch;
+    svx_takes st;
+    if (n_dist) st.add_up(&d_dist, dist, n_dist); else st.add(&d_dist, 1);
+    st.add_up(&d_doff, dist_off.data(), n_parts);
+    st.add_up(&d_loff, label_off.data(), n_parts);
+    st.add_up(&d_soff, scratch_off.data(), n_parts);
+    st.add_up(&d_nm, n_members, n_parts);
+    st.add(&d_lab, n_lab);
+    st.add(&d_scratch, n_scratch ? n_scratch : 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(cut_timed(ctx, d_dist, d_nm, d_doff, d_loff, d_soff, d_scratch, n_parts, cutoff, d_lab, group_min, pl));
+    SVX_TRY(svx_download(ctx, labels, d_lab, n_lab));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }

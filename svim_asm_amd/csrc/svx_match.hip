@@ -293,8 +293,7 @@ int launch_all(svx_ctx* ctx, MatchArgs a, const MatchPlan& pl) {
         a.class_hi = kGroupClasses[c].hi;
         lo = kGroupClasses[c].hi + 1;
         if (!pl.class_lds[c]) continue;
-        const int rc = kGroupClasses[c].threads == 64 ? launch_group<64>(ctx, a, pl.class_lds[c]) : launch_group<256>(ctx, a, pl.class_lds[c]);
-        if (rc != SVX_OK) return rc;
+        SVX_TRY(kGroupClasses[c].threads == 64 ? launch_group<64>(ctx, a, pl.class_lds[c]) : launch_group<256>(ctx, a, pl.class_lds[c]));
     }
     return SVX_OK;
 }
@@ -332,44 +331,37 @@ extern "C" int svx_match_greedy_batch(svx_ctx* ctx, const uint32_t* dist, const 
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n_scratch = pl.n_scratch ? pl.n_scratch : 1;
-    const size_t need = svx_take_bytes(pl.n_dist, 4) + 2 * svx_take_bytes(n_parts, 4) + 4 * svx_take_bytes(n_parts, 8) +
-                        svx_take_bytes(pl.n_b, 4) + svx_take_bytes(pl.n_c, 4) + svx_take_bytes(n_scratch, 1);
-    int rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    uint32_t* d_dist = svx_stage_take<uint32_t>(ctx, pl.n_dist);
-    uint32_t* d_nb = svx_stage_take<uint32_t>(ctx, n_parts);
-    uint32_t* d_nc = svx_stage_take<uint32_t>(ctx, n_parts);
-    uint64_t* d_doff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_boff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_coff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint64_t* d_soff = svx_stage_take<uint64_t>(ctx, n_parts);
-    uint32_t* d_mb = svx_stage_take<uint32_t>(ctx, pl.n_b);
-    uint32_t* d_mc = svx_stage_take<uint32_t>(ctx, pl.n_c);
-    char* d_scratch = svx_stage_take<char>(ctx, n_scratch);
-    SVX_HIP(ctx, hipMemcpyAsync(d_dist, dist, pl.n_dist * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_nb, n_base, (size_t)n_parts * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_nc, n_comp, (size_t)n_parts * 4, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t *d_dist, *d_nb, *d_nc, *d_mb, *d_mc;
+    uint64_t *d_doff, *d_boff, *d_coff, *d_soff;
+    char* d_scratch;
+    svx_takes st;
+    st.add_up(&d_dist, dist, pl.n_dist);
+    st.add_up(&d_nb, n_base, n_parts);
+    st.add_up(&d_nc, n_comp, n_parts);
+    st.add(&d_doff, n_parts);
+    st.add(&d_boff, n_parts);
+    st.add(&d_coff, n_parts);
+    st.add(&d_soff, n_parts);
+    st.add(&d_mb, pl.n_b);
+    st.add(&d_mc, pl.n_c);
+    st.add(&d_scratch, n_scratch);
+    SVX_TRY(svx_stage_lay(ctx, st));
     SVX_HIP(ctx, hipMemsetAsync(d_mb, 0xFF, pl.n_b * 4, ctx->stream));
     SVX_HIP(ctx, hipMemsetAsync(d_mc, 0xFF, pl.n_c * 4, ctx->stream));
     MatchArgs a;
     a.dist = d_dist; a.n_base = d_nb; a.n_comp = d_nc; a.dist_off = d_doff; a.base_off = d_boff; a.comp_off = d_coff;
     a.scratch_off = d_soff; a.scratch = d_scratch; a.n_parts = n_parts; a.match_base = d_mb; a.match_comp = d_mc;
     a.group_min = group_min; a.class_lo = a.class_hi = 0;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
     hipLaunchKernelGGL(k_match_offsets, dim3(1), dim3(256), 0, ctx->stream, d_nb, d_nc, n_parts, group_min, d_doff, d_boff,
                        d_coff, d_soff);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
-    rc = launch_all(ctx, a, pl);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(match_base, d_mb, pl.n_b * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(match_comp, d_mc, pl.n_c * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_timing_mark(ctx, 1));
+    SVX_TRY(launch_all(ctx, a, pl));
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    SVX_TRY(svx_timing_end(ctx));
+    SVX_TRY(svx_download(ctx, match_base, d_mb, pl.n_b));
+    SVX_TRY(svx_download(ctx, match_comp, d_mc, pl.n_c));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }

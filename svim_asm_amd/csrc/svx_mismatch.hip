@@ -181,8 +181,7 @@ int mismatch(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_
     if (n_bases && !bases) return SVX_E_INVALID;
     if (cap && (!out.aln || !out.ref_pos || !out.qry_pos || !out.ref_base || !out.qry_base)) return SVX_E_INVALID;
     uint64_t n_ops;
-    int rc = svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, &n_ops);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_lift_check_offsets(ctx, who, aln_off, n_aln, cigar, d_pool, pool_ops, &n_ops));
     std::vector<uint64_t> tile_off((size_t)n_aln + 1, 0);
     uint64_t most = 0;  // no more events than columns inside both lengths
     for (uint32_t a = 0; a < n_aln; ++a) {
@@ -218,58 +217,45 @@ int mismatch(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_
     }
     const uint64_t rows = cap < most ? cap : most;  // no more rows are ever written
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_stage_reserve(ctx, (d_pool ? 0 : svx_take_bytes(n_ops, 4)) + 3 * svx_take_bytes((size_t)n_aln + 1, 8) +
-                                    2 * svx_take_bytes(n_aln, 8) + 3 * svx_take_bytes(n_aln, 4) +
-                                    svx_take_bytes(kPadFront + n_bases + kPadBack, 1) + 3 * svx_take_bytes(rows, 4) +
-                                    2 * svx_take_bytes(rows, 1));
-    if (rc != SVX_OK) return rc;
-    rc = svx_ws_reserve(ctx, 2 * svx_take_bytes(n_ops, 8) + 2 * svx_take_bytes(n_chunks, sizeof(svx_use)) +
-                                 svx_take_bytes(n_tiles * kThreads, 2) + 2 * svx_take_bytes(n_tiles + 1, sizeof(svx_use)));
-    if (rc != SVX_OK) return rc;
     const uint32_t* d_cigar = d_pool;
-    if (!d_pool) {
-        uint32_t* up = svx_stage_take<uint32_t>(ctx, n_ops);
-        SVX_HIP(ctx, hipMemcpyAsync(up, cigar, n_ops * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_cigar = up;
-    }
-    uint64_t* d_off = svx_stage_take<uint64_t>(ctx, (size_t)n_aln + 1);
-    uint64_t* d_tile_off = svx_stage_take<uint64_t>(ctx, (size_t)n_aln + 1);
-    uint64_t* d_ref_off = svx_stage_take<uint64_t>(ctx, n_aln);
-    uint64_t* d_qry_off = svx_stage_take<uint64_t>(ctx, n_aln);
-    int32_t* d_start = svx_stage_take<int32_t>(ctx, n_aln);
-    uint32_t* d_ref_len = svx_stage_take<uint32_t>(ctx, n_aln);
-    uint32_t* d_qry_len = svx_stage_take<uint32_t>(ctx, n_aln);
-    uint8_t* d_padded = svx_stage_take<uint8_t>(ctx, kPadFront + n_bases + kPadBack);
+    uint64_t *d_off, *d_tile_off, *d_ref_off, *d_qry_off, *d_pref, *d_pqry;
+    int32_t* d_start;
+    uint32_t *d_ref_len, *d_qry_len;
+    uint8_t* d_padded;
     svx_mismatch_soa d_out;
-    d_out.aln = svx_stage_take<uint32_t>(ctx, rows);
-    d_out.ref_pos = svx_stage_take<uint32_t>(ctx, rows);
-    d_out.qry_pos = svx_stage_take<uint32_t>(ctx, rows);
-    d_out.ref_base = svx_stage_take<uint8_t>(ctx, rows);
-    d_out.qry_base = svx_stage_take<uint8_t>(ctx, rows);
-    uint64_t* d_pref = svx_ws_take<uint64_t>(ctx, n_ops);
-    uint64_t* d_pqry = svx_ws_take<uint64_t>(ctx, n_ops);
-    svx_use* d_sum = svx_ws_take<svx_use>(ctx, n_chunks);
-    svx_use* d_base = svx_ws_take<svx_use>(ctx, n_chunks);
-    uint16_t* d_lane_off = svx_ws_take<uint16_t>(ctx, n_tiles * kThreads);
-    svx_use* d_tile_sum = svx_ws_take<svx_use>(ctx, n_tiles + 1);
-    svx_use* d_tile_base = svx_ws_take<svx_use>(ctx, n_tiles + 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, aln_off, ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_tile_off, tile_off.data(), ((size_t)n_aln + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_ref_off, ref_off, (size_t)n_aln * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_qry_off, qry_off, (size_t)n_aln * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_start, ref_start, (size_t)n_aln * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_ref_len, ref_len, (size_t)n_aln * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_qry_len, qry_len, (size_t)n_aln * 4, hipMemcpyHostToDevice, ctx->stream));
+    uint16_t* d_lane_off;
+    svx_use *d_sum, *d_base, *d_tile_sum, *d_tile_base;
+    svx_takes st, ws;
+    if (!d_pool) st.add_up(&d_cigar, cigar, n_ops);
+    st.add_up(&d_off, aln_off, (size_t)n_aln + 1);
+    st.add_up(&d_tile_off, tile_off.data(), (size_t)n_aln + 1);
+    st.add_up(&d_ref_off, ref_off, n_aln);
+    st.add_up(&d_qry_off, qry_off, n_aln);
+    st.add_up(&d_start, ref_start, n_aln);
+    st.add_up(&d_ref_len, ref_len, n_aln);
+    st.add_up(&d_qry_len, qry_len, n_aln);
+    st.add(&d_padded, kPadFront + n_bases + kPadBack);
+    st.add(&d_out.aln, rows);
+    st.add(&d_out.ref_pos, rows);
+    st.add(&d_out.qry_pos, rows);
+    st.add(&d_out.ref_base, rows);
+    st.add(&d_out.qry_base, rows);
+    ws.add(&d_pref, n_ops);
+    ws.add(&d_pqry, n_ops);
+    ws.add(&d_sum, n_chunks);
+    ws.add(&d_base, n_chunks);
+    ws.add(&d_lane_off, n_tiles * kThreads);
+    ws.add(&d_tile_sum, n_tiles + 1);
+    ws.add(&d_tile_base, n_tiles + 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_ws_lay(ctx, ws));
     // (the loads never use a padding byte, but they fetch it: written like every other word)
     SVX_HIP(ctx, hipMemsetAsync(d_padded, 0, kPadFront, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_padded + kPadFront, bases, n_bases, hipMemcpyHostToDevice, ctx->stream));
+    SVX_TRY(svx_upload(ctx, d_padded + kPadFront, bases, n_bases));
     SVX_HIP(ctx, hipMemsetAsync(d_padded + kPadFront + n_bases, 0, kPadBack, ctx->stream));
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_lift_prefixes(ctx, d_cigar, n_ops, d_sum, d_base, d_pref, d_pqry);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_lift_prefixes(ctx, d_cigar, n_ops, d_sum, d_base, d_pref, d_pqry));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     Args g;
     g.cigar = d_cigar;
     g.aln_off = d_off;
@@ -290,25 +276,22 @@ int mismatch(svx_ctx* ctx, const char* who, const uint32_t* cigar, const uint32_
     g.cap = rows;
     hipLaunchKernelGGL(k_mismatch<false>, dim3((uint32_t)n_tiles), dim3(kThreads), 0, ctx->stream, g);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_lift_exclusive(ctx, d_tile_sum, (uint32_t)n_tiles + 1, d_tile_base);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_lift_exclusive(ctx, d_tile_sum, (uint32_t)n_tiles + 1, d_tile_base));
     hipLaunchKernelGGL(k_mismatch<true>, dim3((uint32_t)n_tiles), dim3(kThreads), 0, ctx->stream, g);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    SVX_TRY(svx_timing_end(ctx));
     svx_use total;
-    SVX_HIP(ctx, hipMemcpyAsync(&total, d_tile_base + n_tiles, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_download(ctx, &total, d_tile_base + n_tiles, 1));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = total.ref;
     const uint64_t k = total.ref < cap ? total.ref : cap;  // (<= rows: total <= most)
     if (k) {
-        SVX_HIP(ctx, hipMemcpyAsync(out.aln, d_out.aln, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.ref_pos, d_out.ref_pos, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.qry_pos, d_out.qry_pos, k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.ref_base, d_out.ref_base, k, hipMemcpyDeviceToHost, ctx->stream));
-        SVX_HIP(ctx, hipMemcpyAsync(out.qry_base, d_out.qry_base, k, hipMemcpyDeviceToHost, ctx->stream));
+        SVX_TRY(svx_download(ctx, out.aln, d_out.aln, k));
+        SVX_TRY(svx_download(ctx, out.ref_pos, d_out.ref_pos, k));
+        SVX_TRY(svx_download(ctx, out.qry_pos, d_out.qry_pos, k));
+        SVX_TRY(svx_download(ctx, out.ref_base, d_out.ref_base, k));
+        SVX_TRY(svx_download(ctx, out.qry_base, d_out.qry_base, k));
         SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return total.ref > cap ? SVX_E_CAPACITY : SVX_OK;

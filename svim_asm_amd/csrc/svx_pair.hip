@@ -912,18 +912,15 @@ int pair_single_launch(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_
     a.target = std::max<uint32_t>((n + grid_max - 1) / grid_max, 1024u);
     const uint32_t grid = (n + a.target - 1) / a.target;
     a.slice_len = ((n + grid - 1) / grid + 63) / 64 * 64;
-    size_t need = svx_take_bytes(n, 8) + svx_take_bytes(2 * (size_t)n, 8) + svx_take_bytes(2 * (size_t)n, 4) +
-                  svx_take_bytes((size_t)grid * kFine, 4) +
-                  svx_take_bytes(2 * grid, 4) + svx_take_bytes(2 * grid, 8);
-    int rc = svx_ws_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
+    svx_takes ws;
+    ws.add(&a.dense, n);
+    ws.add(&a.gkey, 2 * (size_t)n);
+    ws.add(&a.gidx, 2 * (size_t)n);
+    ws.add(&a.rows, (size_t)grid * kFine);
+    ws.add(&a.win, 2 * grid);
+    ws.add(&a.win_keys, 2 * grid);
+    SVX_TRY(svx_ws_lay(ctx, ws));
     a.keys = d_keys;
-    a.dense = svx_ws_take<uint64_t>(ctx, n);
-    a.gkey = svx_ws_take<uint64_t>(ctx, 2 * (size_t)n);
-    a.gidx = svx_ws_take<uint32_t>(ctx, 2 * (size_t)n);
-    a.rows = svx_ws_take<uint32_t>(ctx, (size_t)grid * kFine);
-    a.win = svx_ws_take<uint32_t>(ctx, 2 * grid);
-    a.win_keys = svx_ws_take<uint64_t>(ctx, 2 * grid);
     a.f = f;
     a.n = n;
     a.live = live;
@@ -935,16 +932,13 @@ int pair_single_launch(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_
     a.counter = reinterpret_cast<uint32_t*>(ctx->ws) + 68 + 2 * (ctx->pair_launches & 1u);
     a.counter_stale = reinterpret_cast<uint32_t*>(ctx->ws) + 68 + 2 * ((ctx->pair_launches & 1u) ^ 1u);
     a.note = reinterpret_cast<uint32_t*>(ctx->ws) + kBarrierNoteWord;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL(k_pair_single, dim3(grid), dim3(1024), kSingleDynLds, ctx->stream, a);
     SVX_HIP(ctx, hipGetLastError());
     ++ctx->pair_launches;  // (only a launch that went out used its set of counters)
     ctx->barrier_pending = true;
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     return svx_timing_end(ctx);
 }
 
@@ -973,28 +967,24 @@ int pair_partition_bits(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32
     const uint32_t part_grid = n <= kSingleBlockMax ? 1u
         : std::min<uint32_t>(std::max<uint32_t>(1u, (uint32_t)ctx->n_cu / 2), (n + 4095) / 4096);
     const size_t hist_words = (size_t)b.passes * b.n_blocks * kBuckets;
-    size_t need = 2 * svx_take_bytes(n, 8) + 2 * svx_take_bytes(n, 4) + svx_take_bytes(hist_words, 4) +
-                  svx_take_bytes(part_grid, 4);
-    int rc = svx_ws_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    b.keys[0] = svx_ws_take<uint64_t>(ctx, n);
-    b.keys[1] = svx_ws_take<uint64_t>(ctx, n);
-    b.idx[0] = svx_ws_take<uint32_t>(ctx, n);
-    b.idx[1] = svx_ws_take<uint32_t>(ctx, n);
-    b.hist = svx_ws_take<uint32_t>(ctx, hist_words);
-    uint32_t* block_tot = svx_ws_take<uint32_t>(ctx, part_grid);
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
+    uint32_t* block_tot;
+    svx_takes ws;
+    ws.add(&b.keys[0], n);
+    ws.add(&b.keys[1], n);
+    ws.add(&b.idx[0], n);
+    ws.add(&b.idx[1], n);
+    ws.add(&b.hist, hist_words);
+    ws.add(&block_tot, part_grid);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    SVX_TRY(svx_timing_begin(ctx));
     if (small) hipLaunchKernelGGL(k_pair_init<8>, dim3(b.n_blocks), dim3(256), 0, ctx->stream, d_keys, b);
     else hipLaunchKernelGGL(k_pair_init<16>, dim3(b.n_blocks), dim3(256), 0, ctx->stream, d_keys, b);
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 1));
     for (uint32_t pass = 0; pass < b.passes; ++pass) {
         if (small) hipLaunchKernelGGL(k_radix_pass<8>, dim3(b.n_blocks), dim3(256), 0, ctx->stream, b, pass);
         else hipLaunchKernelGGL(k_radix_pass<16>, dim3(b.n_blocks), dim3(256), 0, ctx->stream, b, pass);
     }
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     PartArgs pa;
     pa.sorted_keys = b.keys[b.passes & 1];
     pa.sorted = b.idx[b.passes & 1];
@@ -1027,9 +1017,10 @@ extern "C" int svx_debug_pair_clk(unsigned long long* out) {
 }
 #endif
 
-extern "C" int svx_pair_partition_dev_bits(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_t max_dist,
-                                           uint64_t key_bits, uint32_t* d_perm, uint32_t* d_part_id,
-                                           uint32_t* d_n_parts) {
+// the argument check of both _dev entries; *done: an empty batch, answered here
+static int pair_dev_check(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_t* d_perm, uint32_t* d_part_id, uint32_t* d_n_parts,
+                          bool* done) {
+    *done = true;
     if (!ctx || !d_n_parts) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) {
@@ -1037,29 +1028,36 @@ extern "C" int svx_pair_partition_dev_bits(svx_ctx* ctx, const uint64_t* d_keys,
         return SVX_OK;
     }
     if (!d_keys || !d_perm || !d_part_id) return SVX_E_INVALID;
+    *done = false;
+    return SVX_OK;
+}
+
+extern "C" int svx_pair_partition_dev_bits(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_t max_dist,
+                                           uint64_t key_bits, uint32_t* d_perm, uint32_t* d_part_id,
+                                           uint32_t* d_n_parts) {
+    bool done;
+    SVX_TRY(pair_dev_check(ctx, d_keys, n, d_perm, d_part_id, d_n_parts, &done));
+    if (done) return SVX_OK;
     return pair_partition_bits(ctx, d_keys, n, max_dist, key_bits, d_perm, d_part_id, d_n_parts);
 }
 
 extern "C" int svx_pair_partition_dev(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n,
                                       uint32_t max_dist, uint32_t* d_perm, uint32_t* d_part_id,
                                       uint32_t* d_n_parts) {
-    if (!ctx || !d_n_parts) return SVX_E_INVALID;
-    SVX_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {
-        SVX_HIP(ctx, hipMemsetAsync(d_n_parts, 0, 4, ctx->stream));
-        return SVX_OK;
-    }
-    if (!d_keys || !d_perm || !d_part_id) return SVX_E_INVALID;
+    bool done;
+    SVX_TRY(pair_dev_check(ctx, d_keys, n, d_perm, d_part_id, d_n_parts, &done));
+    if (done) return SVX_OK;
     // which key bits are used is not known here: one reduction and an 8-byte read-back (synchronises)
-    int rc = svx_ws_reserve(ctx, svx_take_bytes(1, 8));
-    if (rc != SVX_OK) return rc;
-    unsigned long long* d_or = reinterpret_cast<unsigned long long*>(svx_ws_take<uint64_t>(ctx, 1));
+    unsigned long long* d_or;
+    svx_takes ws;
+    ws.add(&d_or, 1);
+    SVX_TRY(svx_ws_lay(ctx, ws));
     SVX_HIP(ctx, hipMemsetAsync(d_or, 0, 8, ctx->stream));
     hipLaunchKernelGGL(k_key_or, dim3(std::min<uint32_t>((n + 255) / 256, (uint32_t)ctx->n_cu * 4u)), dim3(256), 0,
                        ctx->stream, d_keys, n, d_or);
     SVX_HIP(ctx, hipGetLastError());
-    uint64_t bits = 0;
-    SVX_HIP(ctx, hipMemcpyAsync(&bits, d_or, 8, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long bits = 0;
+    SVX_TRY(svx_download(ctx, &bits, d_or, 1));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return pair_partition_bits(ctx, d_keys, n, max_dist, bits, d_perm, d_part_id, d_n_parts);
 }
@@ -1073,33 +1071,33 @@ extern "C" int svx_pair_partition(svx_ctx* ctx, const uint64_t* keys, uint32_t n
     SVX_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t bits = 0;  // the keys are here: which bits are in use costs one pass over host memory
     for (uint32_t i = 0; i < n; ++i) bits |= keys[i];
-    size_t need = svx_take_bytes(n, 8) + 2 * svx_take_bytes(n, 4) + svx_take_bytes(1, 4);
-    int rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    uint64_t* d_k = svx_stage_take<uint64_t>(ctx, n);
-    uint32_t* d_p = svx_stage_take<uint32_t>(ctx, n);
-    uint32_t* d_id = svx_stage_take<uint32_t>(ctx, n);
-    uint32_t* d_np = svx_stage_take<uint32_t>(ctx, 1);
-    SVX_HIP(ctx, hipMemcpyAsync(d_k, keys, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = pair_partition_bits(ctx, d_k, n, max_dist, bits, d_p, d_id, d_np);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(perm, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(part_id, d_id, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(n_parts, d_np, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rc = svx_barrier_check(ctx);
+    uint64_t* d_k;
+    uint32_t *d_p, *d_id, *d_np;
+    svx_takes st;
+    st.add_up(&d_k, keys, n);
+    st.add(&d_p, n);
+    st.add(&d_id, n);
+    st.add(&d_np, 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    // the sort, the results down and the wait for them
+    auto run = [&]() -> int {
+        SVX_TRY(pair_partition_bits(ctx, d_k, n, max_dist, bits, d_p, d_id, d_np));
+        SVX_TRY(svx_download(ctx, perm, d_p, n));
+        SVX_TRY(svx_download(ctx, part_id, d_id, n));
+        SVX_TRY(svx_download(ctx, n_parts, d_np, 1));
+        SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return SVX_OK;
+    };
+    SVX_TRY(run());
+    int rc = svx_barrier_check(ctx);
     if (rc != SVX_E_HIP || ctx->pair_wait_free) return rc;
     // A wait between the workgroups of that launch ran out (its other workgroups were not resident in time: too
     // many tenants on the device).  The keys are still staged: run the call again on the plan that never waits
     // inside a launch — radix passes and the partition sweep as two launches — instead of failing it.
     ctx->pair_wait_free = true;
-    rc = pair_partition_bits(ctx, d_k, n, max_dist, bits, d_p, d_id, d_np);
+    rc = run();
     ctx->pair_wait_free = false;
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(perm, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(part_id, d_id, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(n_parts, d_np, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SVX_TRY(rc);
     ctx->err[0] = 0;
     ++ctx->pair_retries;
     return SVX_OK;

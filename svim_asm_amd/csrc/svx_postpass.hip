@@ -69,12 +69,25 @@ static uint64_t post_uniform_stride(const uint32_t* read_off, uint32_t n_reads) 
     return stride * n_reads <= (64ull << 20) ? stride : 0;
 }
 
-size_t svx_postpass_ws_need(const uint32_t* read_off, uint32_t n_reads) {
+// the workspace of the post-passes, added to `ws`: scratch slices of one size for all reads when that is cheap (returned;
+// reads have a handful of segments: no offset table, one launch less), otherwise (0) a table of offsets before the slices
+static uint64_t post_ws_takes(svx_takes& ws, const uint32_t* read_off, uint32_t n_reads, char** d_scratch, uint64_t** d_soff) {
     const uint64_t stride = post_uniform_stride(read_off, n_reads);
-    if (stride) return svx_take_bytes((size_t)n_reads * stride, 1);
+    if (stride) {
+        ws.add(d_scratch, (size_t)n_reads * stride);
+        return stride;
+    }
     uint64_t n_scratch = 0;
     for (uint32_t r = 0; r < n_reads; ++r) n_scratch += svx_align_up(post_scratch_bytes(read_off[r + 1] - read_off[r]), 16);
-    return svx_take_bytes((size_t)n_reads + 1, 8) + svx_take_bytes(n_scratch ? n_scratch : 1, 1);
+    ws.add(d_soff, (size_t)n_reads + 1);
+    ws.add(d_scratch, n_scratch ? n_scratch : 1);
+    return 0;
+}
+
+size_t svx_postpass_ws_need(const uint32_t* read_off, uint32_t n_reads) {
+    svx_takes ws;
+    post_ws_takes(ws, read_off, n_reads, (char**)nullptr, (uint64_t**)nullptr);
+    return ws.bytes();
 }
 
 // shared front end: validates the host copy of read_off / out_off and lays out the per-read scratch slices
@@ -103,8 +116,7 @@ static int post_plan(svx_ctx* ctx, const uint32_t* read_off, uint32_t n_reads, c
 int svx_postpass_plan(svx_ctx* ctx, const uint32_t* read_off, uint32_t n_reads, const uint64_t* out_off, uint64_t* stride) {
     std::vector<uint64_t> scratch_off;
     uint64_t n_scratch = 0;
-    int rc = post_plan(ctx, read_off, n_reads, out_off, &scratch_off, &n_scratch);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(post_plan(ctx, read_off, n_reads, out_off, &scratch_off, &n_scratch));
     *stride = post_uniform_stride(read_off, n_reads);
     return SVX_OK;
 }
@@ -118,25 +130,17 @@ extern "C" int svx_segments_postpass_dev(svx_ctx* ctx, const svx_raw* d_raw, con
     if (!read_off || !d_read_off || !out_off || !d_out_off || !d_out_cnt || (n_contigs && !d_contig_rank)) return SVX_E_INVALID;
     std::vector<uint64_t> scratch_off;
     uint64_t n_scratch = 0;
-    int rc = post_plan(ctx, read_off, n_reads, out_off, &scratch_off, &n_scratch);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(post_plan(ctx, read_off, n_reads, out_off, &scratch_off, &n_scratch));
     if (read_off[n_reads] && (!d_raw || !d_out)) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    rc = svx_ws_reserve(ctx, svx_postpass_ws_need(read_off, n_reads));
-    if (rc != SVX_OK) return rc;
-    // scratch slices: one size for all reads when that is cheap (reads have a handful of segments: no offset table,
-    // one launch less); otherwise laid out on the device from d_read_off.  Nothing of this call's host memory is
+    // the slices without a common size are laid out on the device from d_read_off.  Nothing of this call's host memory is
     // read after it returns: the call is asynchronous
-    const uint64_t stride = post_uniform_stride(read_off, n_reads);
     uint64_t* d_soff = nullptr;
     char* d_scratch;
-    if (stride) {
-        d_scratch = svx_ws_take<char>(ctx, (size_t)n_reads * stride);
-    } else {
-        d_soff = svx_ws_take<uint64_t>(ctx, (size_t)n_reads + 1);
-        d_scratch = svx_ws_take<char>(ctx, n_scratch ? n_scratch : 1);
-        hipLaunchKernelGGL(k_post_scratch_offsets, dim3(1), dim3(256), 0, ctx->stream, d_read_off, n_reads, d_soff);
-    }
+    svx_takes ws;
+    const uint64_t stride = post_ws_takes(ws, read_off, n_reads, &d_scratch, &d_soff);
+    SVX_TRY(svx_ws_lay(ctx, ws));
+    if (!stride) hipLaunchKernelGGL(k_post_scratch_offsets, dim3(1), dim3(256), 0, ctx->stream, d_read_off, n_reads, d_soff);
     PostArgs a;
     a.scratch_stride = stride;
     a.raw = d_raw; a.read_off = d_read_off; a.n_reads = n_reads; a.contig_rank = d_contig_rank; a.n_contigs = n_contigs;
@@ -153,63 +157,43 @@ extern "C" int svx_segments_postpass(svx_ctx* ctx, const svx_raw* raw, const uin
     if (!ctx || !params) return SVX_E_INVALID;
     if (n_reads == 0) return SVX_OK;
     if (!read_off || !out_off || !out_cnt || (n_contigs && !contig_rank)) return SVX_E_INVALID;
-    if (read_off[0] != 0) return SVX_E_INVALID;
-    std::vector<uint64_t> scratch_off(n_reads);
+    std::vector<uint64_t> scratch_off;
     uint64_t n_scratch = 0;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        if (read_off[r + 1] < read_off[r] || out_off[r + 1] < out_off[r]) {
-            SVX_SET_ERR(ctx, "read_off / out_off must be non-decreasing (index %u)", r);
-            return SVX_E_INVALID;
-        }
-        const uint32_t s = read_off[r + 1] - read_off[r];
-        if (out_off[r + 1] - out_off[r] < post_bound(s)) {
-            SVX_SET_ERR(ctx, "read %u: %llu output slots for %u segment slots, svx_segments_postpass_bound() = %llu", r,
-                        (unsigned long long)(out_off[r + 1] - out_off[r]), s, (unsigned long long)post_bound(s));
-            return SVX_E_CAPACITY;
-        }
-        scratch_off[r] = n_scratch;
-        n_scratch += svx_align_up(post_scratch_bytes(s), 16);
-    }
+    SVX_TRY(post_plan(ctx, read_off, n_reads, out_off, &scratch_off, &n_scratch));
     const uint32_t n_segs = read_off[n_reads];
     const uint64_t n_out = out_off[n_reads];
     if (n_segs && (!raw || !out)) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    size_t need = svx_take_bytes(n_segs ? n_segs : 1, sizeof(svx_raw)) + svx_take_bytes((size_t)n_reads + 1, 4) +
-                  svx_take_bytes(n_contigs ? n_contigs : 1, 4) + svx_take_bytes(n_out ? n_out : 1, sizeof(svx_post)) +
-                  2 * svx_take_bytes((size_t)n_reads + 1, 8) + svx_take_bytes(n_reads, 4) +
-                  svx_take_bytes(n_scratch ? n_scratch : 1, 1);
-    int rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
+    svx_raw* d_raw;
+    uint32_t *d_off, *d_cnt;
+    int32_t* d_rank;
+    svx_post* d_out;
+    uint64_t *d_ooff, *d_soff;
+    char* d_scratch;
+    svx_takes st;
+    if (n_segs) st.add_up(&d_raw, raw, n_segs); else st.add(&d_raw, 1);
+    st.add_up(&d_off, read_off, (size_t)n_reads + 1);
+    if (n_contigs) st.add_up(&d_rank, contig_rank, n_contigs); else st.add(&d_rank, 1);
+    st.add(&d_out, n_out ? n_out : 1);
+    st.add_up(&d_ooff, out_off, (size_t)n_reads + 1);
+    st.add(&d_soff, (size_t)n_reads + 1);
+    st.add(&d_cnt, n_reads);
+    st.add(&d_scratch, n_scratch ? n_scratch : 1);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_upload(ctx, d_soff, scratch_off.data(), n_reads));
     PostArgs a;
-    svx_raw* d_raw = svx_stage_take<svx_raw>(ctx, n_segs ? n_segs : 1);
-    uint32_t* d_off = svx_stage_take<uint32_t>(ctx, (size_t)n_reads + 1);
-    int32_t* d_rank = svx_stage_take<int32_t>(ctx, n_contigs ? n_contigs : 1);
-    svx_post* d_out = svx_stage_take<svx_post>(ctx, n_out ? n_out : 1);
-    uint64_t* d_ooff = svx_stage_take<uint64_t>(ctx, (size_t)n_reads + 1);
-    uint64_t* d_soff = svx_stage_take<uint64_t>(ctx, (size_t)n_reads + 1);
-    uint32_t* d_cnt = svx_stage_take<uint32_t>(ctx, n_reads);
-    char* d_scratch = svx_stage_take<char>(ctx, n_scratch ? n_scratch : 1);
-    if (n_segs) SVX_HIP(ctx, hipMemcpyAsync(d_raw, raw, (size_t)n_segs * sizeof(svx_raw), hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, read_off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (n_contigs) SVX_HIP(ctx, hipMemcpyAsync(d_rank, contig_rank, (size_t)n_contigs * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_ooff, out_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_soff, scratch_off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, ctx->stream));
     a.raw = d_raw; a.read_off = d_off; a.n_reads = n_reads; a.contig_rank = d_rank; a.n_contigs = n_contigs;
     a.min_sv = params->min_sv_size; a.max_sv = params->max_sv_size;
     a.out = d_out; a.out_off = d_ooff; a.out_cnt = d_cnt; a.scratch = d_scratch; a.scratch_off = d_soff;
     a.scratch_stride = 0;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL(k_segments_post, dim3((n_reads + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, a);
     SVX_HIP(ctx, hipGetLastError());
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_end(ctx);
-    if (rc != SVX_OK) return rc;
-    if (n_out) SVX_HIP(ctx, hipMemcpyAsync(out, d_out, (size_t)n_out * sizeof(svx_post), hipMemcpyDeviceToHost, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(out_cnt, d_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SVX_TRY(svx_timing_mark(ctx, 2));
+    SVX_TRY(svx_timing_end(ctx));
+    SVX_TRY(svx_download(ctx, out, d_out, n_out));
+    SVX_TRY(svx_download(ctx, out_cnt, d_cnt, n_reads));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }

@@ -39,13 +39,13 @@ extern "C" int svx_segments_classify_dev(svx_ctx* ctx, const svx_seg* d_segs, ui
         return SVX_E_INVALID;
     }
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_ws_reserve(ctx, svx_take_bytes(n_segs, sizeof(svx_seg)));
-    if (rc != SVX_OK) return rc;
     SegArgs a;
+    svx_takes ws;
+    ws.add(&a.sorted, n_segs);
+    SVX_TRY(svx_ws_lay(ctx, ws));
     a.seg_rl = nullptr;
     a.read_len_out = nullptr;
     a.segs = d_segs;
-    a.sorted = svx_ws_take<svx_seg>(ctx, n_segs);
     a.read_off = d_read_off;
     a.read_len = d_read_len;
     a.n_reads = n_reads;
@@ -53,13 +53,10 @@ extern "C" int svx_segments_classify_dev(svx_ctx* ctx, const svx_seg* d_segs, ui
     a.out = d_out;
     uint32_t blocks = (n_reads + 31) / 32;  // eight lanes per read
     uint32_t cap = (uint32_t)ctx->n_cu * 8u;
-    rc = svx_timing_begin(ctx);
-    if (rc != SVX_OK) return rc;
-    rc = svx_timing_mark(ctx, 1);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_begin(ctx));
+    SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL(k_segments, dim3(blocks < cap ? blocks : cap), dim3(256), 0, ctx->stream, a);
-    rc = svx_timing_mark(ctx, 2);
-    if (rc != SVX_OK) return rc;
+    SVX_TRY(svx_timing_mark(ctx, 2));
     SVX_HIP(ctx, hipGetLastError());
     return svx_timing_end(ctx);
 }
@@ -79,20 +76,18 @@ extern "C" int svx_segments_classify(svx_ctx* ctx, const svx_seg* segs, const ui
     if (n_segs == 0) return SVX_OK;
     if (!segs || !out || read_off[0] != 0) return SVX_E_INVALID;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    size_t need = svx_take_bytes(n_segs, sizeof(svx_seg)) + svx_take_bytes((size_t)n_reads + 1, 4) +
-                  svx_take_bytes(n_reads, 4) + svx_take_bytes(n_segs, sizeof(svx_raw));
-    int rc = svx_stage_reserve(ctx, need);
-    if (rc != SVX_OK) return rc;
-    svx_seg* d_s = svx_stage_take<svx_seg>(ctx, n_segs);
-    uint32_t* d_off = svx_stage_take<uint32_t>(ctx, (size_t)n_reads + 1);
-    int32_t* d_rl = svx_stage_take<int32_t>(ctx, n_reads);
-    svx_raw* d_o = svx_stage_take<svx_raw>(ctx, n_segs);
-    SVX_HIP(ctx, hipMemcpyAsync(d_s, segs, (size_t)n_segs * sizeof(svx_seg), hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_off, read_off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SVX_HIP(ctx, hipMemcpyAsync(d_rl, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = svx_segments_classify_dev(ctx, d_s, n_segs, d_off, n_reads, d_rl, params, d_o);
-    if (rc != SVX_OK) return rc;
-    SVX_HIP(ctx, hipMemcpyAsync(out, d_o, (size_t)n_segs * sizeof(svx_raw), hipMemcpyDeviceToHost, ctx->stream));
+    svx_seg* d_s;
+    uint32_t* d_off;
+    int32_t* d_rl;
+    svx_raw* d_o;
+    svx_takes st;
+    st.add_up(&d_s, segs, n_segs);
+    st.add_up(&d_off, read_off, (size_t)n_reads + 1);
+    st.add_up(&d_rl, read_len, n_reads);
+    st.add(&d_o, n_segs);
+    SVX_TRY(svx_stage_lay(ctx, st));
+    SVX_TRY(svx_segments_classify_dev(ctx, d_s, n_segs, d_off, n_reads, d_rl, params, d_o));
+    SVX_TRY(svx_download(ctx, out, d_o, n_segs));
     SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVX_OK;
 }

@@ -15,6 +15,7 @@ documented rows are written, the bytes behind them stay as they were.  The last 
 family's call on what another family's bigger call left, a workspace that grows — on fresh contexts, without the hook.
 """
 import functools
+import random
 import zlib
 
 import numpy as np
@@ -22,10 +23,15 @@ import pytest
 
 from oracle import orc, svim_oracle
 from svim_asm_amd import _lib, synth
-from tests import helpers, sam_text_writer as stw, tabix_reader
+from tests import callable_cases, cover_cases, helpers, lift_restatement, match_cases, mismatch_restatement
+from tests import sam_text_writer as stw, tabix_reader
+from tests import test_gpu_callable as tcall
 from tests import test_gpu_collect as tcol
 from tests import test_gpu_editdist as ted
+from tests import test_gpu_cover as tcov
 from tests import test_gpu_inflate as tinf
+from tests import test_gpu_lift as tlift
+from tests import test_gpu_mismatch as tmis
 from tests import test_gpu_pair as tpair
 from tests import test_gpu_sam as tsam
 from tests import test_gpu_segments as tseg
@@ -371,6 +377,118 @@ def test_linkage_cut_batch(svx_ctx, case, cutoff):
         poisoned(svx_ctx, lambda _: svx_ctx.linkage_cut_batch(dist, counts, cutoff), _check_labels(exp))
     finally:
         svx_ctx.set_linkage_group_min(0)
+
+
+# ------------------------------------------------------------------------------------------ match, cover, lift, mismatch
+def test_match_greedy_batch(svx_ctx):
+    """Under the default threshold of nine pairs: 2 x 4 stays with the lane kernel, 33 x 65 goes to the group kernel."""
+    dist, n_base, n_comp, want_base, want_comp = match_cases.batch([("ties", 2, 4), ("wide", 33, 65)])
+    assert want_base.count(_lib.MATCH_NONE) < len(want_base)
+
+    def check(got, _):
+        assert got[0].tolist() == want_base and got[1].tolist() == want_comp
+    svx_ctx.set_match_group_min(0)
+    poisoned(svx_ctx, lambda _: svx_ctx.match_greedy_batch(dist, n_base, n_comp), check)
+
+
+@functools.lru_cache(maxsize=None)
+def _cover_case():
+    """1025 lists — tests/callable_cases.many_lists: one more than a pass of the offsets kernel of svx_cover_single takes —,
+    list 7 replaced by one of 1025 entries, one more than a pass of the scans takes: both carry once."""
+    rng = random.Random(1025)
+    n = cover_cases.CHUNK + 1
+    lists = list(callable_cases.many_lists(n))
+    lists[7] = [(s, e) for s, e in cover_cases.random_list(rng, n, contigs=(0,), contig_len=20000) if s < e]
+    while len(lists[7]) < n:  # (svx_cover_single takes no empty interval)
+        lists[7] = sorted(lists[7] + [(lists[7][0][0], lists[7][0][1] + len(lists[7]))])
+    queries = cover_cases.random_queries(rng, 65, contigs=(0,), contig_len=20000, longest=200)
+    callable_cases.check_inputs(lists)
+    cover_cases.check_inputs(lists, queries)
+    assert len(lists) == n and len(lists[7]) == n
+    where = lift_restatement.locate(lists, queries)
+    bits = [[int(i != lift_restatement.NONE) for i in row] for row in where]
+    assert bits == cover_cases.R.cover(lists, queries) and 0 < sum(bits[7]) < len(queries) and any(any(r) for r in bits[8:])
+    return lists, queries, bits, where, callable_cases.R.flat(callable_cases.R.single(lists))
+
+
+def test_cover_query(svx_ctx):
+    lists, queries, bits, _, _ = _cover_case()
+    poisoned(svx_ctx, lambda _: svx_ctx.cover_query(*tcov.arrays(lists, queries)),
+             lambda got, _: np.testing.assert_array_equal(got, np.array(bits, np.uint8)))
+
+
+def test_cover_locate(svx_ctx):
+    lists, queries, _, where, _ = _cover_case()
+    poisoned(svx_ctx, lambda _: svx_ctx.cover_locate(*tcov.arrays(lists, queries)),
+             lambda got, _: np.testing.assert_array_equal(got, np.array(where, np.uint32)))
+
+
+def test_cover_single(svx_ctx):
+    lists, _, _, _, segments = _cover_case()
+    assert 0 < len(segments[0]) < sum(len(ivs) for ivs in lists)
+
+    def check(got, _):
+        assert tuple(x.tolist() for x in got) == tuple(segments)
+    poisoned(svx_ctx, lambda _: svx_ctx.cover_single(*tcall.arrays(lists)), check)
+
+
+@functools.lru_cache(maxsize=None)
+def _lift_case():
+    """Two alignments of 700 ops: the pool spans two chunks of the prefix scan, the second alignment lies across their border."""
+    rng = random.Random(700)
+    inputs = tlift.with_queries(rng, [(rng.randrange(0, 5000), tlift.random_ops(rng, 700)) for _ in range(2)])
+    assert _lib.LIFT_CHUNK < len(inputs[0]) <= 2 * _lib.LIFT_CHUNK and int(inputs[1][1]) < _lib.LIFT_CHUNK
+    query, state = lift_restatement.lift_batch(*inputs)
+    assert {lift_restatement.OUTSIDE, lift_restatement.ALIGNED, lift_restatement.DELETED, lift_restatement.END} <= set(state)
+    return inputs, query, state
+
+
+def _with_pool_in_hbm(ctx, words, call):
+    """call(pointer, n_ops) on the pool in HBM, words behind the alignments' last one included."""
+    pool = ctx.dev_array(np.concatenate((words, np.full(7, (9 << 4) | 0, np.uint32))))
+    try:
+        return call(pool.ptr, len(words) + 7)
+    finally:
+        pool.free()
+
+
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_cigar_lift(svx_ctx, form):
+    inputs, query, state = _lift_case()
+
+    def run(_):
+        if form == "host":
+            return svx_ctx.cigar_lift(*inputs)
+        return _with_pool_in_hbm(svx_ctx, inputs[0], lambda ptr, n: svx_ctx.cigar_lift(ptr, *inputs[1:], n_ops=n))
+
+    def check(got, _):
+        assert got[1].tolist() == state and got[0].tolist() == query
+    poisoned(svx_ctx, run, check)
+
+
+@functools.lru_cache(maxsize=None)
+def _mismatch_case():
+    """Two alignments, of 1025 and 300 ops: two chunks of the prefix scan, and the first one's window is more than a tile."""
+    inputs = tmis.pool_of((1025, 300), 1325)
+    assert _lib.LIFT_CHUNK < len(inputs[0]) <= 2 * _lib.LIFT_CHUNK and tmis.T < int(inputs[5][0]) and int(inputs[5][1]) > 0
+    expected = mismatch_restatement.mismatch_batch(*inputs)
+    assert set(expected["aln"]) == {0, 1} and max(p - int(inputs[2][0]) for p, a in zip(expected["ref_pos"], expected["aln"]) if a == 0) >= tmis.T
+    return inputs, expected
+
+
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_cigar_mismatch(svx_ctx, form):
+    inputs, expected = _mismatch_case()
+
+    def run(_):
+        if form == "host":
+            return svx_ctx.cigar_mismatch(*inputs)
+        return _with_pool_in_hbm(svx_ctx, inputs[0], lambda ptr, n: svx_ctx.cigar_mismatch(ptr, *inputs[1:], n_ops=n))
+
+    def check(got, _):
+        for k in tmis.COLS:
+            assert got[k].tolist() == expected[k], k
+    poisoned(svx_ctx, run, check)
 
 
 # ----------------------------------------------------------------------------------------------------- collect
