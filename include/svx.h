@@ -872,6 +872,54 @@ int svx_cigar_mismatch_dev(svx_ctx* ctx, const uint32_t* d_cigar, uint64_t n_ops
                            uint32_t n_aln, const uint8_t* bases, uint64_t n_bases, const uint64_t* ref_off, const uint32_t* ref_len,
                            const uint64_t* qry_off, const uint32_t* qry_len, svx_mismatch_soa out, uint64_t cap, uint64_t* n_out);
 
+/*
+ * Left shift of small gaps, batched: how many columns can insertion or deletion e move to the left inside its alignment
+ * without changing the aligned haplotype?  `bases`, `ref_off`, `ref_len`, `qry_off`, `qry_len` and `ref_start` are
+ * svx_cigar_mismatch's.  An event is one row of svx_cigar_extract: ev_aln its alignment, ev_ref_pos / ev_qry_pos the row's
+ * ref_pos / read_pos (the first reference position and SEQ offset behind the gap's left edge), ev_len its length, ev_type
+ * SVX_SIG_INS or SVX_SIG_DEL; ev_limit is the most steps the event may take — the entry reads no CIGAR, the caller states
+ * how far an event may move (up to the column behind the previous gap, say).  With a = ev_aln[e], ref = bases + ref_off[a],
+ * qry = bases + qry_off[a], r = ev_ref_pos[e] - ref_start[a], q = ev_qry_pos[e], L = ev_len[e] and up(x) = x & 0xDF, the
+ * definition is this loop:
+ *     k = 0
+ *     while k < ev_limit[e]:
+ *         i = k + 1
+ *         stop unless i <= r, i <= q, r - i < ref_len[a], q - i < qry_len[a]
+ *         R = up(ref[r - i]);  Q = up(qry[q - i])              the aligned column the gap would pass
+ *         stop unless R is one of 'A' 'C' 'G' 'T' and R == Q
+ *         INS: stop unless q + L - i < qry_len[a];  X = up(qry[q + L - i])
+ *         DEL: stop unless r + L - i < ref_len[a];  X = up(ref[r + L - i])
+ *         stop unless X == R
+ *         k = i
+ *     shift[e] = k
+ * The shifted event is (ev_ref_pos - k, ev_qry_pos - k, L), an insertion's bases SEQ[ev_qry_pos - k .. ev_qry_pos - k + L).
+ * A step whose indices fall outside a range stops the walk: no byte outside [ref_off, ref_off + ref_len) or [qry_off,
+ * qry_off + qry_len) takes part in a result.  Events come in any order; shift[e] depends on event e alone and is identical
+ * from run to run.
+ * All pointers are HOST pointers; the call returns with `shift` written.  SVX_E_INVALID — nothing launched, the context
+ * usable, the message names the alignment or the event — for ev_aln >= n_aln, ev_ref_pos < ref_start, a type that is neither
+ * SVX_SIG_INS nor SVX_SIG_DEL, ev_len == 0, a negative ref_start, and ref_off + ref_len or qry_off + qry_len above n_bases.
+ * n_ev == 0, n_aln == 0 (without events) and ev_limit == 0 are valid.  SVX_E_TOO_LARGE for more than 2^31 - 257 events.
+ * Two forms with identical outputs: one LANE per event walks at most `lane_steps` steps (svx_ctx_set_shift_lane_steps); the
+ * events that still match with steps left are listed, in event order and without atomics (a workgroup scan, one exclusive
+ * sum over workgroups), the host reads the count back, and one WAVE per listed event goes on from there,
+ * SVX_SHIFT_WAVE_COLS steps per iteration (four bytes of each stream per lane) and one ballot of the failing lanes.  Three
+ * launches, and a fourth where the list is not empty.
+ */
+#define SVX_SHIFT_WAVE_COLS 256
+int svx_indel_shift(svx_ctx* ctx, const uint8_t* bases, uint64_t n_bases, const uint64_t* ref_off, const uint32_t* ref_len,
+                    const uint64_t* qry_off, const uint32_t* qry_len, const int32_t* ref_start, uint32_t n_aln,
+                    const uint32_t* ev_aln, const uint32_t* ev_ref_pos, const uint32_t* ev_qry_pos, const uint32_t* ev_len,
+                    const uint8_t* ev_type, const uint32_t* ev_limit, uint32_t n_ev, uint32_t* shift);
+/* Steps the lane form walks before it hands an event that still matches to the wave form.  A negative value restores the
+ * default SVX_SHIFT_LANE_STEPS (8: on the one batch measured — 10^6 synthetic events, one in a thousand with a shift of 100
+ * to 5000 — the kernels take 0.080 / 0.081 / 0.083 / 0.086 / 0.095 ms at 4 / 8 / 16 / 32 / 64 steps, 0.47 ms with the wave
+ * form alone and 1.08 ms with the lane form alone; 8 is the flat bottom's value that keeps every shift of the fixture in
+ * the lane form); 0 sends every event with a positive limit to the wave form; INT32_MAX keeps every event
+ * in the lane form. */
+#define SVX_SHIFT_LANE_STEPS 8
+int svx_ctx_set_shift_lane_steps(svx_ctx* ctx, int32_t steps);
+
 #ifdef __cplusplus
 }
 #endif

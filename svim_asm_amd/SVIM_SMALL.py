@@ -6,8 +6,10 @@ Per haplotype, over the records COLLECT visits that store their bases and hold n
     interval) and ONE svx_cigar_mismatch over the CIGAR pool of the whole file, records outside the batch with both
     lengths 0;
   * indels: ONE svx_cigar_extract with min_len 1; the ops shorter than --min_sv_size are kept (the longer ones are
-    svim-asm's);
-  * alleles, upper case and where the aligner put them — nothing is left-aligned or normalised: SNV (POS = ref_pos + 1),
+    svim-asm's); with --left_align ONE svx_indel_shift per batch, on the batch's pool of bases, moves each of them as far
+    to the left as its bases allow without passing another gap (DESIGN.md §3.19);
+  * alleles, upper case and where the aligner put them — nothing is left-aligned unless --left_align, and nothing is
+    normalised beyond that: SNV (POS = ref_pos + 1),
     INS and DEL anchored on the base in front (POS = ref_pos); an indel at its alignment's first reference position
     (no_anchor) and an allele with a base outside ACGT (ambiguous_base) are dropped and counted;
   * an event is kept only when its REF span lies inside ONE single-coverage segment of its haplotype
@@ -127,7 +129,34 @@ def _haplotype_events(s, hap_list, reference, contigs, options, ctx, counts):
     used = used[g_of[used] >= 0]  # (a record without reference bases has neither columns nor indels)
     pos = np.maximum(np.asarray(r.pos, dtype=np.int64), 0).astype(np.int32)  # (unplaced records: both lengths 0)
     pool = _device_pool(r)
-    # ---- mismatches
+    # ---- indel rows: every I and D op where the aligner put it
+    n_ops = np.diff(cig_off)[used]
+    sub_off = np.zeros(len(used) + 1, np.uint64)
+    np.cumsum(n_ops, out=sub_off[1:])
+    total = int(sub_off[-1])
+    words = cigar[np.repeat(cig_off[used], n_ops) + np.arange(total) - np.repeat(sub_off[:-1].astype(np.int64), n_ops)] if total else cigar[:0]
+    sig = ctx.cigar_extract(words, sub_off, pos[used], min_len=1) if len(used) else None
+    if sig is None:
+        sig = {k: np.zeros(0, np.int64) for k in ("aln", "ref_pos", "read_pos", "len", "type")}
+    s_aln, s_pos, s_len = (np.asarray(sig[k], dtype=np.int64) for k in ("aln", "ref_pos", "len"))
+    s_ins = np.asarray(sig["type"]) == 0  # SVX_SIG_INS
+    small = s_len < int(options.min_sv_size)
+    i_sub = s_aln[small]  # (ascending: the rows come in (alignment, op) order)
+    i_rec = used[i_sub]
+    i_pos = s_pos[small]
+    i_qry = np.asarray(sig["read_pos"], dtype=np.int64)[small]
+    i_len = s_len[small]
+    i_ins = s_ins[small]
+    left_align = bool(getattr(options, "left_align", False))
+    if left_align:
+        # the most steps of a row: up to the column behind the gap in front of it (large ones included) or behind its
+        # alignment's start, in the original placement — a gap never passes another one and keeps one aligned column
+        prev_end = pos[used[s_aln]].astype(np.int64)
+        same = s_aln[1:] == s_aln[:-1]
+        prev_end[1:][same] = (s_pos + np.where(s_ins, 0, s_len))[:-1][same]
+        i_limit = np.maximum(0, s_pos - prev_end - 1)[small]
+        i_shift = np.zeros(len(i_rec), np.int64)
+    # ---- mismatches, and with --left_align the small rows' shifts on the same pool of bases
     parts = []
     for first, last in _batches((end_of - start_of + l_seq)[used], int(options.batch_bases)):
         b = used[first:last]
@@ -145,27 +174,22 @@ def _haplotype_events(s, hap_list, reference, contigs, options, ctx, counts):
         else:
             ev = ctx.cigar_mismatch(cigar, cig_off, pos, bases, ref_off, ref_len, qry_off, qry_len)
         parts.append(ev)
+        if left_align:
+            lo, hi = (int(x) for x in np.searchsorted(i_sub, (first, last)))
+            if hi > lo:
+                i_shift[lo:hi] = ctx.indel_shift(bases, ref_off, ref_len, qry_off, qry_len, pos, i_rec[lo:hi], i_pos[lo:hi], i_qry[lo:hi],
+                                                 i_len[lo:hi], np.where(i_ins[lo:hi], 0, 1), i_limit[lo:hi])
     cat = lambda key, dtype: np.concatenate([np.asarray(p[key], dtype=dtype) for p in parts]) if parts else np.zeros(0, dtype)
     m_aln = cat("aln", np.int64)
     counts["mismatches"] = int(len(m_aln))
     snv = _Events(g_of[m_aln], cat("ref_pos", np.int64) + 1, cat("ref_base", np.uint8).view("S1").astype("S%d" % width),
                   cat("qry_base", np.uint8).view("S1").astype("S%d" % width), np.zeros(len(m_aln), np.int8))
     # ---- indels
-    n_ops = np.diff(cig_off)[used]
-    sub_off = np.zeros(len(used) + 1, np.uint64)
-    np.cumsum(n_ops, out=sub_off[1:])
-    total = int(sub_off[-1])
-    words = cigar[np.repeat(cig_off[used], n_ops) + np.arange(total) - np.repeat(sub_off[:-1].astype(np.int64), n_ops)] if total else cigar[:0]
-    sig = ctx.cigar_extract(words, sub_off, pos[used], min_len=1) if len(used) else None
-    if sig is None:
-        sig = {k: np.zeros(0, np.int64) for k in ("aln", "ref_pos", "read_pos", "len", "type")}
-    small = np.asarray(sig["len"], dtype=np.int64) < int(options.min_sv_size)
-    i_rec = used[np.asarray(sig["aln"], dtype=np.int64)[small]]
-    i_pos = np.asarray(sig["ref_pos"], dtype=np.int64)[small]
-    i_qry = np.asarray(sig["read_pos"], dtype=np.int64)[small]
-    i_len = np.asarray(sig["len"], dtype=np.int64)[small]
-    i_ins = np.asarray(sig["type"])[small] == 0  # SVX_SIG_INS
     counts["small_indels"] = int(len(i_rec))
+    if left_align:
+        i_pos, i_qry = i_pos - i_shift, i_qry - i_shift
+        counts["left_aligned"] = int((i_shift > 0).sum())
+        counts["shifted_bases"] = int(i_shift.sum())
     anchored = i_pos > start_of[i_rec]
     counts["no_anchor"] = int((~anchored).sum())
     i_rec, i_pos, i_qry, i_len, i_ins = i_rec[anchored], i_pos[anchored], i_qry[anchored], i_len[anchored], i_ins[anchored]
@@ -254,6 +278,7 @@ def summarise(records, gt, counts):
         calls = np.char.add(np.char.add(calls, b"|"), _GT_TEXT[gt[h]])
     texts, n = np.unique(calls, return_counts=True) if len(records) else ([], [])
     order = ("records_used", "no_sequence", "spliced", "mismatches", "small_indels") + DROPS
+    order += tuple(k for k in ("left_aligned", "shifted_bases") if counts and k in counts[0])  # (--left_align)
     return {"haplotypes": [{k: int(c[k]) for k in order} for c in counts], "records": int(len(records)),
             "by_type": {name: int((records.kind == k).sum()) for k, name in enumerate(KINDS)},
             "by_genotype": {t.decode(): int(k) for t, k in zip(texts, n)}}

@@ -131,6 +131,9 @@ COVER_NONE = 0xFFFFFFFF          # SVX_COVER_NONE: cover_locate's "no entry cove
 LIFT_OUTSIDE, LIFT_ALIGNED, LIFT_DELETED, LIFT_END = range(4)  # SVX_LIFT_*: cigar_lift's states
 LIFT_CHUNK = 1024                # SVX_LIFT_CHUNK: ops per workgroup of cigar_lift's scan, chunk sums per pass of its second level
 MISMATCH_TILE = 4096             # SVX_MISMATCH_TILE: reference positions of one alignment per workgroup of cigar_mismatch
+SHIFT_WAVE_COLS = 256            # SVX_SHIFT_WAVE_COLS: steps one iteration of indel_shift's wave form tests
+SHIFT_LANE_STEPS = 8             # SVX_SHIFT_LANE_STEPS: steps of indel_shift's lane form before the hand-over (default)
+SHIFT_LANES_ONLY = 0x7FFFFFFF    # set_shift_lane_steps: every event stays in the lane form
 COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 MATCH_LDS_PAIRS = 32768          # SVX_MATCH_LDS_PAIRS: largest matrix the matching group kernel keeps in LDS
@@ -214,6 +217,8 @@ SYMBOLS = {
                                      C.POINTER(C.c_uint64)]),
     "svx_cigar_mismatch_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, MismatchSoa,
                                          C.c_uint64, C.POINTER(C.c_uint64)]),
+    "svx_indel_shift": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    "svx_ctx_set_shift_lane_steps": (C.c_int, [_P, C.c_int32]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -410,6 +415,11 @@ class Context:
         """Fewest pairs of a partition match_greedy_batch assigns with one workgroup instead of one lane (0: the
         default; MATCH_LANES_ONLY: none)."""
         self._check(self.lib.svx_ctx_set_match_group_min(self.h, int(pairs)))
+
+    def set_shift_lane_steps(self, steps):
+        """Steps indel_shift walks with one lane per event before a wave takes the event over (negative: the default
+        SHIFT_LANE_STEPS; 0: every event with a positive limit to the wave form; SHIFT_LANES_ONLY: none)."""
+        self._check(self.lib.svx_ctx_set_shift_lane_steps(self.h, int(steps)))
 
     # ---------------------------------------------------------------- device buffers
     def dev_array(self, host=None, nbytes=None):
@@ -913,6 +923,26 @@ class Context:
             self._check(rc)
             k = min(int(n.value), cap)
             return {key: v[:k] for key, v in out.items()}
+
+    def indel_shift(self, bases, ref_off, ref_len, qry_off, qry_len, ref_start, aln, ref_pos, qry_pos, length, type, limit):
+        """How many columns every small gap can move to the left inside its alignment (svx_indel_shift in include/svx.h):
+        a uint32 per event.  `bases`, `ref_off`, `ref_len`, `qry_off`, `qry_len` and `ref_start` as for cigar_mismatch; an
+        event is a row of cigar_extract (aln, ref_pos, read_pos, len, type) with the most steps it may take in `limit`."""
+        bases = _as(bases, np.uint8)
+        ref_off, qry_off = _as(ref_off, np.uint64), _as(qry_off, np.uint64)
+        ref_len, qry_len = _as(ref_len, np.uint32), _as(qry_len, np.uint32)
+        ref_start = _as(ref_start, np.int32)
+        n_aln = len(ref_start)
+        if any(len(x) != n_aln for x in (ref_off, ref_len, qry_off, qry_len)):
+            raise SvxError(SVX_E_INVALID, "one ref_off, ref_len, qry_off, qry_len and ref_start per alignment")
+        ev = [_as(x, np.uint32) for x in (aln, ref_pos, qry_pos, length)] + [_as(type, np.uint8), _as(limit, np.uint32)]
+        n_ev = len(ev[0])
+        if any(len(x) != n_ev for x in ev):
+            raise SvxError(SVX_E_INVALID, "one aln, ref_pos, qry_pos, length, type and limit per event")
+        shift = np.zeros(n_ev, np.uint32)
+        self._check(self.lib.svx_indel_shift(self.h, _ptr(bases), len(bases), _ptr(ref_off), _ptr(ref_len), _ptr(qry_off),
+                                             _ptr(qry_len), _ptr(ref_start), n_aln, *[_ptr(x) for x in ev], n_ev, _ptr(shift)))
+        return shift
 
     def cover_single(self, start_key, end_key, list_off):
         """The ranges on which exactly ONE entry of a list — and the same one throughout — lies over the reference, per

@@ -46,6 +46,7 @@ struct svx_ctx {
     bool split_chain = false;               // svx_ctx_set_split_chain: the split-segment chain as three launches
     uint32_t link_group_min = 0;            // svx_ctx_set_linkage_group_min: smallest partition of the group kernel (0: default)
     uint32_t match_group_min = 0;           // svx_ctx_set_match_group_min: fewest pairs of the matching group kernel (0: default)
+    int32_t shift_lane_steps = -1;          // svx_ctx_set_shift_lane_steps: steps of the lane form of svx_indel_shift (< 0: default)
     char err[512] = {0};
 };
 

@@ -5,7 +5,8 @@
 HAP1 and HAP2 are the alignments of the sample's haplotype assemblies to GENOME (BAM, SAM, or PAF with --query1 /
 --query2).  Every aligned column that differs from the reference and every inserted or deleted run shorter than
 --min_sv_size becomes a record where exactly one alignment of its haplotype lies over it; the aligner's placement of an
-indel stands.  OUT_DIR gets small.vcf (one sample column, GT phased: haplotype 1 | haplotype 2; small.vcf.gz and its index
+indel stands unless --left_align is given, which shifts each one leftmost on the device, so that two assemblies that
+place the same indel differently give one record.  OUT_DIR gets small.vcf (one sample column, GT phased: haplotype 1 | haplotype 2; small.vcf.gz and its index
 with --bgzip_output) and summary.json."""
 import argparse
 import logging
@@ -30,6 +31,9 @@ def parse(argv):
                    help="Insertions and deletions of this size or more are left to svim-asm (default: %(default)s)")
     p.add_argument("--batch_bases", type=int, default=1 << 28,
                    help="Most reference plus assembly bases compared in one device call (default: %(default)s)")
+    p.add_argument("--left_align", action="store_true",
+                   help="Move every insertion and deletion shorter than --min_sv_size as far to the left as its bases allow, "
+                        "never past another gap of its alignment (default: the aligner's placement stands)")
     p.add_argument("--bgzip_output", action="store_true", help="Write small.vcf.gz and its tabix index instead of small.vcf")
     p.add_argument("--no_bgzf_crc", action="store_true", help="Do not check the CRC32 of the BGZF members of a BAM")
     p.add_argument("--device", type=int, default=0, help="HIP device index of the GPU to use")
