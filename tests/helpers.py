@@ -489,6 +489,45 @@ def oracle_backed_device(monkeypatch):
     return ctx
 
 
+# ---- intended segments as the records of one submission (tests/test_gpu_collect.py, tests/test_gpu_segments_cases.py)
+def segment_cigar(q_start, q_end, read_len, rev, insertion=False):
+    """BAM CIGAR words `{lead}S{len}M{tail}S` of the segment [q_start, q_end) of a read of read_len bases, in the
+    record's orientation (a reverse record's leading clip is the read's tail); `insertion`: 50 inserted bases inside
+    the match, so that the segment is 50 shorter on the reference."""
+    m = q_end - q_start
+    lead, tail = (read_len - q_end, q_start) if rev else (q_start, read_len - q_end)
+    cig = [(lead << 4) | 4] if lead else []
+    if insertion:
+        cig += [((m - 60) << 4) | 0, (50 << 4) | 1, (10 << 4) | 0]
+    else:
+        cig += [(m << 4) | 0]
+    cig += [(tail << 4) | 4] if tail else []
+    return np.array(cig, np.uint32)
+
+
+def chimeric_batch(rng, words, ref_start, extra, seg_src, seg_tid, seg_pos, seg_rev, counts, n_unrelated, rank):
+    """The arguments of svx_collect_batch for chimeric reads given segment by segment: seg_src[j] >= 0 names the pool
+    record words[seg_src[j]] (at ref_start[seg_src[j]]), -1 - x the SA-derived alignment extra[x]; counts: segments per
+    read.  The pool records are dealt among n_unrelated random records in random order."""
+    order = rng.permutation(len(words) + n_unrelated)
+    pool, pool_rs, where = [], [], {}
+    for slot in order.tolist():
+        if slot < len(words):
+            where[slot] = len(pool); pool.append(words[slot]); pool_rs.append(ref_start[slot])
+        else:
+            t = random_cigar(rng, int(rng.integers(1, 40)))
+            pool.append(np.array([(l << 4) | o for o, l in t], np.uint32)); pool_rs.append(int(rng.integers(0, 1 << 27)))
+    n_aln = len(pool)
+    src = np.array([where[x] if x >= 0 else n_aln + (-1 - x) for x in seg_src], np.uint32)
+    aln_off = np.concatenate(([0], np.cumsum([len(w) for w in pool]))).astype(np.uint64)
+    extra_off = np.concatenate(([0], np.cumsum([len(w) for w in extra]))).astype(np.uint64)
+    return dict(parts=[np.concatenate(pool)], aln_off=aln_off, ref_start=np.array(pool_rs, np.int32),
+                extra_cigar=np.concatenate(extra) if extra else np.zeros(0, np.uint32), extra_off=extra_off, seg_src=src,
+                seg_tid=np.array(seg_tid, np.int32), seg_pos=np.array(seg_pos, np.int32), seg_rev=np.array(seg_rev, np.uint8),
+                seg_qend=np.full(len(src), -1, np.int32), read_off=np.concatenate(([0], np.cumsum(counts))).astype(np.uint32),
+                rank=rank)
+
+
 # ---- COLLECT of one submission by the checker alone (tests/test_gpu_collect.py)
 _POST_CODE = {1: "TANDEM", 2: "DUP_INT", 3: "INV"}
 _POST_WIDTH = {"TANDEM": 5, "DUP_INT": 6, "INV": 4}

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import orc, svim_oracle
 from svim_asm_amd import _lib
+from tests.segments_cases import DISTINCT  # all six parameters differ pairwise
 
 pytestmark = pytest.mark.gpu
 DEFAULT = (40, 100000, 50, 50, 50, 50)  # min_sv, max_sv, qgt, qot, rgt, rot (SVIM_input_parsing.py defaults)
@@ -50,7 +51,7 @@ def random_reads(rng, n_reads, max_k, n_contigs=3, spread=300):
 def test_random_reads_match_oracle(svx_ctx, seed):
     rng = np.random.default_rng(seed)
     segs, off, rl = random_reads(rng, n_reads=int(rng.integers(1, 3000)), max_k=int(rng.choice([2, 6, 40, 90])))
-    for params in (DEFAULT, (40, 1000, 50, 50, 50, 50), (50, 20, 0, 0, 0, 0), (1, 100000, 500, 500, 500, 500)):
+    for params in (DEFAULT, (40, 1000, 50, 50, 50, 50), (50, 20, 0, 0, 0, 0), (1, 100000, 500, 500, 500, 500), DISTINCT):
         got = svx_ctx.segments_classify(segs, off, rl, params)
         exp = orc.segments_classify(segs, off, rl, params)
         assert np.array_equal(got, exp)
@@ -133,25 +134,25 @@ def test_postpass_matches_record_level_oracle(svx_ctx, seed):
             for name_, v in zip(("kind", "a0", "a1", "a2", "a3", "a4", "a5"), row):
                 raw[k][name_] = v
             k += 1
-    prm = (40, 100000, 50, 50, 50, 50) if seed % 2 == 0 else (10, 300, 50, 50, 50, 50)
-    post, first = svx_ctx.segments_postpass(raw, read_off, rank, prm)
     code = {1: "TANDEM", 2: "DUP_INT", 3: "INV"}
     width = {"TANDEM": 5, "DUP_INT": 6, "INV": 4}
-    kinds = set()
-    for i, r in enumerate(reads):
-        exp = svim_oracle.postpass_records(r, rank.tolist(), prm[0], prm[1])
-        got = []
-        for rec in post[first[i]:first[i + 1]]:
-            kind = code[int(rec["kind"])]
-            vals = [int(rec[n]) for n in ("a0", "a1", "a2", "a3", "a4", "a5")][:width[kind]]
-            if kind == "TANDEM":
-                vals[4] = bool(vals[4])
-            if kind == "INV":
-                vals[3] = bool(vals[3])
-            got.append((kind,) + tuple(vals))
-        assert got == exp, (i, r)
-        kinds |= {(t[0], t[-1]) if t[0] == "INV" else (t[0],) for t in exp}
-    assert {("TANDEM",), ("DUP_INT",), ("INV", True), ("INV", False)} <= kinds
+    for prm in ((40, 100000, 50, 50, 50, 50) if seed % 2 == 0 else (10, 300, 50, 50, 50, 50), DISTINCT):
+        post, first = svx_ctx.segments_postpass(raw, read_off, rank, prm)
+        kinds = set()
+        for i, r in enumerate(reads):
+            exp = svim_oracle.postpass_records(r, rank.tolist(), prm[0], prm[1])
+            got = []
+            for rec in post[first[i]:first[i + 1]]:
+                kind = code[int(rec["kind"])]
+                vals = [int(rec[n]) for n in ("a0", "a1", "a2", "a3", "a4", "a5")][:width[kind]]
+                if kind == "TANDEM":
+                    vals[4] = bool(vals[4])
+                if kind == "INV":
+                    vals[3] = bool(vals[3])
+                got.append((kind,) + tuple(vals))
+            assert got == exp, (i, r)
+            kinds |= {(t[0], t[-1]) if t[0] == "INV" else (t[0],) for t in exp}
+        assert {("TANDEM",), ("DUP_INT",), ("INV", True), ("INV", False)} <= kinds
 
 
 def test_postpass_capacity_is_checked(svx_ctx):
