@@ -121,13 +121,18 @@ def test_tile_and_round_boundaries(svx_ctx, n_ops):
     rng = np.random.default_rng(n_ops)
     ops = rng.integers(0, 3, size=n_ops)
     lens = rng.integers(30, 60, size=n_ops)
-    cig = ((lens << 4) | ops).astype(np.uint32)
-    # one long alignment, then the same ops cut at awkward places (starts at tile/lane edges)
-    for cuts in ([], [1], [n_ops // 2], [15, 16, 17, 1024, 4096]):
-        cuts = sorted(set(c for c in cuts if 0 < c < n_ops))
-        off = np.array([0] + cuts + [n_ops], dtype=np.uint64)
-        rs = np.arange(len(off) - 1, dtype=np.int32) * 1000
-        assert_same(svx_ctx.cigar_extract(cig, off, rs, 40), orc.cigar_extract(cig, off, rs, 40))
+    dense = ((lens << 4) | ops).astype(np.uint32)   # M, I, D alike: about 44 % of the ops qualify, every tile is dense
+    # M-heavy, about 3 % qualifying: some 30 signatures per round, no round fills its queue and a tile of 4096 ops
+    # carries 123 on average — the staged walk, on either side of the slab's 128
+    ops = rng.choice(3, size=n_ops, p=[0.955, 0.0225, 0.0225])
+    staged = ((rng.integers(30, 60, size=n_ops) << 4) | ops).astype(np.uint32)
+    for cig in (dense, staged):
+        # one long alignment, then the same ops cut at awkward places (starts at tile/lane edges)
+        for cuts in ([], [1], [n_ops // 2], [15, 16, 17, 1024, 4096]):
+            cuts = sorted(set(c for c in cuts if 0 < c < n_ops))
+            off = np.array([0] + cuts + [n_ops], dtype=np.uint64)
+            rs = np.arange(len(off) - 1, dtype=np.int32) * 1000
+            assert_same(svx_ctx.cigar_extract(cig, off, rs, 40), orc.cigar_extract(cig, off, rs, 40))
 
 
 def test_dense_all_indel_tiles_take_the_direct_path(svx_ctx):
