@@ -23,33 +23,40 @@
 //                             carry to signatures that precede the tile's first alignment start
 //                             and ref_start of the alignment.
 //   D  k_cigar_dense          dense tiles (> 128 signatures, e.g. adversarial all-indel CIGARs) are
-//                             re-walked with carry-in and output base known (process_tile<DIRECT>),
-//                             writing final SoA; an empty launch in the common case.
+//                             re-walked with carry-in and output base known, one workgroup per tile and
+//                             one wave per round (dense_tile_wg), writing final SoA; an empty launch in
+//                             the common case.
 // Batches of at most 8 M ops (both haplotype BAMs of an assembly: what the svim-asm CLI launches) take a two-launch
 // variant of the same code: k_cigar_tiles with tiles of 1024 ops and the tile's start index from a wave
 // search, then k_cigar_finish_small, in which every workgroup scans all (folded) descriptors itself, finishes its
-// own 16 tiles and re-walks its share of the dense ones, dealt out round-robin (see the comment above that kernel).
+// own 16 tiles and re-walks its share of the dense ones (process_tile<MODE_DIRECT>, a wave per one-round tile), dealt out
+// round-robin (see the comment above that kernel).
+// One carry runs through all of it: SegCarry {has_start, ref, read, count} under OpSeg is what a round hands the next,
+// what a tile descriptor, a folded descriptor, blk_agg and blk_prefix hold, and what the scans scan (wave_scan of
+// svx_scan_dev.h).  Three places keep the same combine written out on scalars, each with its reason beside it: the
+// round-to-round carry of process_tile, fold_group_desc, and the folds across waves in k_desc_scan and
+// k_cigar_finish_small.
 // With chimeric reads in the submission (svx_collect_batch_dev) the split-segment chain of SVIM_inter.py:62-340 rides
 // inside these launches (a3_chain_block): rows + decision tree in the tile launch of the two-launch path
 // (k_tiles_a3) or in the finish launch of the streaming path (k_finish_a3), the post-passes in the last launch.
 // Output order = (alignment, op) order by construction (prefix sums, no atomically-ordered appends).
 #include "svx_internal.h"
 #include "svx_postpass_dev.h"
+#include "svx_scan_dev.h"
 #include "svx_segments_dev.h"
 
 namespace {
 
-#ifndef SVX_LANE_OPS
 #define SVX_LANE_OPS 16
-#endif
-constexpr int kLaneOps = SVX_LANE_OPS;          // consecutive ops per lane per round (16 or 32)
+constexpr int kLaneOps = SVX_LANE_OPS;          // consecutive ops per lane per round
 constexpr int kLU = kLaneOps / 4;              // uint4 groups per lane per round
 constexpr int kRoundOps = 64 * kLaneOps;       // 1024 ops per wave round (4 KiB)
-#ifndef SVX_ROUNDS
 #define SVX_ROUNDS 4
-#endif
 constexpr int kRounds = SVX_ROUNDS;
 constexpr int kTileOps = kRoundOps * kRounds;  // 4096 ops per tile (16 KiB)
+// a lane's start bits of one round are a 16-bit field, a tile's four rounds two registers; the per-round queue aliases
+// the start mask's LDS; k_cigar_dense walks a tile's rounds with one wave each
+static_assert(kLaneOps == 16 && kRounds == 4, "16 ops per lane and 4 rounds per tile are built into the walk");
 #ifndef SVX_SLAB
 #define SVX_SLAB 128
 #endif
@@ -57,10 +64,7 @@ constexpr int kTileOps = kRoundOps * kRounds;  // 4096 ops per tile (16 KiB)
 // once (one burst per tile) and read once: a 2 KiB stride instead of 4 KiB is worth 5 % of the
 // streaming kernel (DRAM locality of the bursts), 1 KiB another 2 % but too tight for SV-dense regions
 constexpr int kSlab = SVX_SLAB;
-#ifndef SVX_WAVES
-#define SVX_WAVES 4
-#endif
-constexpr int kWaves = SVX_WAVES;              // waves (= tiles) per workgroup
+constexpr int kWaves = 4;                      // waves (= tiles) per workgroup
 constexpr int kXposeU4 = 64 * kLU;             // transpose buffer: kLU uint4 per lane, XOR-swizzled
 constexpr int kScanBlock = 1024;               // tile descriptors per scan workgroup
 
@@ -157,27 +161,49 @@ __device__ __forceinline__ void store_final(const CigarArgs& p, uint64_t slot, u
     }
 }
 
-// DPP lane movement (gfx9 family): identity 0 flows into lanes without a source.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShr4 = 0x114, kDppShr8 = 0x118;
-constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143, kDppWaveShr1 = 0x138;
+// ---- the values and operators this file hands to wave_scan (svx_scan_dev.h).  An operator takes (later range, range
+// in front of it); all-zero is its identity, which is what lanes without a DPP source receive. ----
 
-// inclusive wave scan: segmented (flag f resets) sums of r and d, plain sum of c
-#define SVX_SEG_STEP(CTRL, RM)                                                     \
-    {                                                                              \
-        const uint32_t f2 = dpp0<CTRL, RM>(f), r2 = dpp0<CTRL, RM>(sr),            \
-                       d2 = dpp0<CTRL, RM>(sd), c2 = dpp0<CTRL, RM>(sc);           \
-        sr += f ? 0u : r2;                                                         \
-        sd += f ? 0u : d2;                                                         \
-        f |= f2;                                                                   \
-        sc += c2;                                                                  \
+// the value of the lane in front (wave_shr:1, lane 0 receives 0): an inclusive scan's exclusive form
+template <typename T>
+__device__ __forceinline__ T lane_before(T incl) { return dpp0<0x138, 0xF>(incl); }
+
+struct OpOr32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; }
+};
+
+// three plain sums side by side
+struct Sum3 {
+    uint32_t r, d, c;
+};
+struct OpSum3 {
+    __device__ __forceinline__ Sum3 operator()(Sum3 a, Sum3 b) const { return Sum3{a.r + b.r, a.d + b.d, a.c + b.c}; }
+};
+
+// The segmented carry of the CIGAR path: over a range of ops (a round, a tile, a group of tiles, a scan block), whether
+// an alignment starts inside it, both cursor sums since the last such start (since the range's first op when there is
+// none) and the number of signatures.  Tile descriptors, the folded descriptors of the two-launch path, blk_agg and
+// blk_prefix are all this tuple.
+struct SegCarry {
+    uint32_t has_start, ref, read, count;
+};
+struct OpSeg {
+    __device__ __forceinline__ SegCarry operator()(SegCarry later, SegCarry front) const {
+        later.ref += later.has_start ? 0u : front.ref;
+        later.read += later.has_start ? 0u : front.read;
+        later.has_start |= front.has_start;
+        later.count += front.count;
+        return later;
     }
-#define SVX_SEG_SCAN()                                                             \
-    SVX_SEG_STEP(kDppShr1, 0xF) SVX_SEG_STEP(kDppShr2, 0xF) SVX_SEG_STEP(kDppShr4, 0xF) \
-    SVX_SEG_STEP(kDppShr8, 0xF) SVX_SEG_STEP(kDppBcast15, 0xA) SVX_SEG_STEP(kDppBcast31, 0xC)
+};
+constexpr uint32_t kDescCount = 0x3FFFFFFFu;    // descriptor .x: the tile's signature count below its two flags
+constexpr uint32_t kDescForceDense = 1u << 30;  // descriptor flag: a round overflowed the queue
+// a tile descriptor {count | force_dense << 30 | seen_head << 31, ref_tail, read_tail, a_lo} as a carry
+__device__ __forceinline__ SegCarry desc_carry(const uint4 v) { return SegCarry{v.x >> 31, v.y, v.z, v.x & kDescCount}; }
+// dense: beyond the slab, or a round beyond the queue — the tile is walked again instead of finished from its slab
+__device__ __forceinline__ bool desc_dense(const uint4 v) {
+    return (v.x & kDescCount) > (uint32_t)kSlab || (v.x & kDescForceDense);
+}
 
 // One round of a tile: lane reads uint4 #(k*64+lane), k = 0..3 (coalesced 1 KiB per wave
 // instruction) through a per-tile buffer resource whose num_records is the tile's valid byte
@@ -199,10 +225,6 @@ __device__ __forceinline__ int xswz(int c) { return (c / (16 / kLU)) & (kLU - 1)
 template <bool SOA>
 __device__ __forceinline__ void load_round(__amdgpu_buffer_rsrc_t rc, __amdgpu_buffer_rsrc_t ro_, uint32_t tile_len,
                                            uint32_t ro, int lane, uint4 (&q)[kLU], uint32_t (&o)[kLU]) {
-#ifdef SVX_EXP_NOLOAD  // perf experiment only: no HBM traffic
-    for (int k = 0; k < kLU; ++k) { q[k] = make_uint4(ro + lane, (400u << 4), (3u << 4) | 1u, (77u << 4)); o[k] = 0; }
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < kLU; ++k) {
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
@@ -229,9 +251,7 @@ __device__ __forceinline__ void load_round(__amdgpu_buffer_rsrc_t rc, __amdgpu_b
 #ifndef SVX_TILE_MIN_WAVES
 #define SVX_TILE_MIN_WAVES 4  // waves per SIMD the register allocator must leave room for
 #endif
-#ifndef SVX_STAGE
 #define SVX_STAGE 64
-#endif
 constexpr int kStage = SVX_STAGE;  // finished records staged in LDS per wave before one burst to the slab (>= kQueue)
 #ifndef SVX_QUEUE
 #define SVX_QUEUE 64  // (32 until round 3: a fifth of the 1024-op rounds of an SV-dense contig overflowed it)
@@ -255,7 +275,6 @@ constexpr int head_words() { return (TILE_OPS / 32) > queue_cap<TILE_OPS>() * 4 
 constexpr int kHeadWords = head_words<kTileOps>();
 // a round's records beyond the stage buffer's room (only a round with more than kStage of them) go straight to the slab
 static_assert(kStage == 64, "drain() moves the stage buffer with one lane per record");
-constexpr uint32_t kDescForceDense = 1u << 30;  // descriptor flag: a round overflowed the queue
 
 enum { WALK_TOTALS = 0, WALK_QUEUE = 1, WALK_DIRECT = 2 };
 
@@ -301,9 +320,6 @@ __device__ __forceinline__ WalkOut walk16(const CigarArgs& p, const uint4* myx, 
     uint32_t rr = 0, rd = 0, base_r = 0, base_d = 0, n_emit = 0, qn = 0;
     uint32_t hs = 0;  // this lane has passed an alignment start
     uint32_t aln_cur = dc.aln0, rs_cur = dc.rs0;  // WALK_DIRECT only
-#ifdef SVX_EXP_NOWALK  // perf experiment only: memory + scan floor without the per-op work
-    { const uint4 v = myx[swz]; WalkOut o; o.tot_r = v.x; o.tot_d = v.y; o.tail_r = v.z; o.tail_d = v.w; o.n_emit = 0; o.n_queued = 0; return o; }
-#endif
     uint4 nxt = myx[swz];
 #pragma unroll 1
     for (int j = 0; j < kLU; ++j) {
@@ -390,11 +406,8 @@ __device__ __forceinline__ WalkOut walk16(const CigarArgs& p, const uint4* myx, 
 }
 
 __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
-    v |= dpp0<kDppShr1, 0xF>(v); v |= dpp0<kDppShr2, 0xF>(v); v |= dpp0<kDppShr4, 0xF>(v);
-    v |= dpp0<kDppShr8, 0xF>(v); v |= dpp0<kDppBcast15, 0xA>(v); v |= dpp0<kDppBcast31, 0xC>(v);
-    return __builtin_amdgcn_readlane(v, 63);
+    return __builtin_amdgcn_readlane(wave_scan(v, OpOr32()), 63);
 }
-
 
 #ifdef SVX_EXP_PROF  // perf experiment only (tools/prof_phases.py): per-tile phase clocks
 constexpr uint32_t kProfTiles = 32768;
@@ -406,11 +419,105 @@ __device__ uint32_t g_prof[kProfTiles * 8];  // 5 phase sums (shader clocks), li
 #define SVX_PROF_ADD(i, d)
 #endif
 
+// ---- the pieces of one round that the wave-per-tile walk (process_tile) and the wave-per-round walk of a dense tile
+// (dense_tile_wg) share ----
+
+// A tile's ops and the two buffer resources its rounds load through.  num_records is the tile's valid byte count (see
+// load_round).  SoA op bytes: the hardware range check works per DWORD, so the resource covers the tile's bytes
+// rounded up to 4 (the op array is read at most 3 bytes past n_ops, inside its last dword; those bytes are masked
+// off in load_round — they would otherwise read as ops of length 0)
+struct TileSpan {
+    uint64_t g0, end;  // global index of the tile's first op, and of the op behind its last
+    uint32_t len;
+    __amdgpu_buffer_rsrc_t rs_c, rs_o;
+};
+template <bool SOA, int TILE_OPS>
+__device__ __forceinline__ TileSpan tile_span(const CigarArgs& p, const uint32_t tile) {
+    TileSpan s;
+    s.g0 = (uint64_t)tile * TILE_OPS;
+    s.end = (s.g0 + TILE_OPS < p.n_ops) ? s.g0 + TILE_OPS : p.n_ops;
+    s.len = (uint32_t)(s.end - s.g0);
+    s.rs_c = make_rsrc(p.cigar + s.g0, s.len * 4u);
+    s.rs_o = make_rsrc(SOA ? (const void*)(p.op + s.g0) : (const void*)p.cigar, SOA ? ((s.len + 3u) & ~3u) : 0u);
+    return s;
+}
+
+// Transpose through wave-private LDS.  uint4 #i of a round (= lane i % 64's load i / 64) belongs to lane c = i / kLU as
+// its p = i % kLU -th group; it is stored at c*kLU + (p ^ xswz(c)), which keeps both the ds_write_b128 and the per-group
+// ds_read_b128 bank-conflict free.  (The loop over a lane's loads stays with the caller: behind a function that takes
+// the loaded registers as an array the streaming kernels schedule differently.)
+__device__ __forceinline__ int xpose_slot(const int i) {
+    const int c = i / kLU;
+    return c * kLU + ((i & (kLU - 1)) ^ xswz(c));
+}
+
+// Wave scans of a round (DPP).  Plain inclusive sums of the lane totals, signature counts and alignment-start counts;
+// the segmentation is applied afterwards: the carry-in of lane l is its exclusive sum plus Q(h) = tail(h) - P(h) of
+// the last lane h < l that holds an alignment start (ballot + one ds_bpermute per cursor), or plus the round's carry
+// — which the wave-per-round walk only knows later, so it is an argument of in_r / in_d and of nothing else.
+struct RoundScan {
+    Sum3 incl;          // .c packs two counters: signatures (low 16 bits, <= 1024) and alignment starts (high 16 bits)
+    uint32_t xr, xd;    // exclusive cursor sums
+    uint32_t xc, xh;    // signatures and alignment starts of the lanes in front
+    uint32_t total;     // wave-uniform: .c of the whole round
+    uint64_t H;         // lanes that hold an alignment start
+    uint32_t qr, qd;    // Q of this lane
+    bool xf;            // a start in an earlier lane of this round
+    uint32_t gq_r, gq_d;  // Q of the last such lane
+    __device__ __forceinline__ uint32_t in_r(const uint32_t carry_r) const { return xr + (xf ? gq_r : carry_r); }  // lane carry-in
+    __device__ __forceinline__ uint32_t in_d(const uint32_t carry_d) const { return xd + (xf ? gq_d : carry_d); }
+};
+// (fills the caller's struct: returned by value, the same statements give the streaming kernels another schedule)
+__device__ __forceinline__ void round_scan(RoundScan& s, const WalkOut& wo, const uint32_t hm, const int lane) {
+    s.incl = wave_scan(Sum3{wo.tot_r, wo.tot_d, wo.n_emit | ((uint32_t)__popc(hm) << 16)}, OpSum3());
+    const Sum3 x = lane_before(s.incl);
+    s.xr = x.r; s.xd = x.d;
+    s.xc = x.c & 0xFFFFu;
+    s.xh = x.c >> 16;
+    s.total = (uint32_t)__builtin_amdgcn_readlane(s.incl.c, 63);
+    s.H = __builtin_amdgcn_ballot_w64(hm != 0);
+    const uint64_t hl = s.H & ((1ull << lane) - 1ull);
+    s.qr = wo.tail_r - s.incl.r;
+    s.qd = wo.tail_d - s.incl.d;
+    s.xf = hl != 0;
+    const int hsrc = s.xf ? 63 - __clzll((long long)hl) : 0;
+    s.gq_r = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)s.qr);
+    s.gq_d = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)s.qd);
+}
+// the round as one range: wave-uniform (dense_tile_wg hands it to the rounds behind; process_tile keeps the same steps
+// on its scalars, see there)
+__device__ __forceinline__ SegCarry round_carry(const RoundScan& s) {
+    const uint32_t R = __builtin_amdgcn_readlane(s.incl.r, 63), D = __builtin_amdgcn_readlane(s.incl.d, 63);
+    const int hlast = s.H ? 63 - __clzll((long long)s.H) : 0;
+    const uint32_t tr = R + __builtin_amdgcn_readlane(s.qr, hlast), td = D + __builtin_amdgcn_readlane(s.qd, hlast);
+    return SegCarry{s.H ? 1u : 0u, s.H ? tr : R, s.H ? td : D, s.total & 0xFFFFu};
+}
+
+// The walk's context: for the first walk of a round (totals or queue) only where the lane is; direct_fill adds what the
+// second walk of a dense tile's round needs — `before` = the range in front of the round, .count the output slot of the
+// round's first signature; `heads_before` = alignment starts inside the tile in front of the round.
+__device__ __forceinline__ DirectCtx direct_ctx(const uint32_t a_lo, const uint64_t g_lane0, const bool dup) {
+    DirectCtx dc;
+    dc.in_r = 0; dc.in_d = 0; dc.out0 = 0; dc.a_lo = a_lo; dc.g_lane0 = g_lane0; dc.aln0 = 0; dc.rs0 = 0; dc.dup = dup;
+    return dc;
+}
+__device__ __forceinline__ void direct_fill(const CigarArgs& p, DirectCtx& dc, const RoundScan& rs, const SegCarry before,
+                                            const uint32_t heads_before) {
+    dc.in_r = rs.in_r(before.ref); dc.in_d = rs.in_d(before.read);
+    dc.out0 = (uint64_t)before.count + rs.xc;
+    // the alignment the lane's first op continues: a_lo - 1 + the starts before the lane inside the tile
+    // (none before the batch's first op: that op is a start itself)
+    dc.aln0 = !dc.dup ? dc.a_lo + heads_before + rs.xh - 1u
+                      : (dc.g_lane0 ? find_aln(p.aln_off, p.n_aln, dc.a_lo, dc.g_lane0 - 1u) : 0xFFFFFFFFu);
+    dc.rs0 = (p.ref_start && dc.aln0 < p.n_aln) ? (uint32_t)p.ref_start[dc.aln0] : 0u;
+}
+
 // What a tile needs from outside.  MODE_STAGE: where a_lo (alignments that start before the tile)
 // comes from; MODE_DIRECT: a_lo, the carry-in and the output base, all known to the caller.
 enum { ALO_TABLE = 0, ALO_SEARCH = 1, ALO_GIVEN = 2 };
 struct TileIn {
-    uint32_t a_lo, carry_r, carry_d, obase;
+    uint32_t a_lo;
+    SegCarry before;  // the range in front of the tile; .count = the tile's output base
 };
 
 // One tile (TILE_OPS <= 4096 ops) processed by one wave.  MODE_STAGE: signatures go to the tile's slab
@@ -420,17 +527,9 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
                                              uint32_t* hmask, uint4* queue, uint4* stage, const TileIn& in) {
     static_assert(TILE_OPS % kRoundOps == 0 && TILE_OPS <= kTileOps, "a tile is 1..kRounds whole rounds");
     uint4* lcarry = xp;  // per-lane carry-ins reuse the transpose buffer once the walk has consumed it
-    const uint64_t g0 = (uint64_t)tile * TILE_OPS;
-    const uint64_t tile_end = (g0 + TILE_OPS < p.n_ops) ? g0 + TILE_OPS : p.n_ops;
-
-    // first round's loads go out before the (latency-bound) alignment-start lookup
-    const uint32_t tile_len = (uint32_t)(tile_end - g0);
-    const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(p.cigar + g0, tile_len * 4u);
-    // SoA op bytes: the hardware range check works per DWORD, so the resource covers the tile's bytes
-    // rounded up to 4 (the op array is read at most 3 bytes past n_ops, inside its last dword; those
-    // bytes are masked off in load_round — they would otherwise read as ops of length 0)
-    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(SOA ? (const void*)(p.op + g0) : (const void*)p.cigar,
-                                                  SOA ? ((tile_len + 3u) & ~3u) : 0u);
+    const TileSpan ts = tile_span<SOA, TILE_OPS>(p, tile);
+    const uint64_t g0 = ts.g0, tile_end = ts.end;
+    const uint32_t tile_len = ts.len;
 #ifdef SVX_EXP_PROF
     uint32_t prof_acc[8] = {};
     const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();
@@ -438,7 +537,8 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
     SVX_PROF_T(t_begin);
     uint4 q[kLU];
     uint32_t qo[kLU] = {};
-    load_round<SOA>(rs_c, rs_o, tile_len, 0u, lane, q, qo);
+    // first round's loads go out before the (latency-bound) alignment-start lookup
+    load_round<SOA>(ts.rs_c, ts.rs_o, tile_len, 0u, lane, q, qo);
 
     // ---- alignment starts inside this tile → 4096-bit mask in LDS; `dup` = two alignments start
     // at the same op (empty alignments), which disables the popcount shortcut for the index ----
@@ -450,7 +550,7 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
     wave_lds_sync();
     bool dup = false;
     // hu: for every round, the op slots (0..kLaneOps-1) at which ANY lane starts an alignment —
-    // gathered here once per tile (kLaneOps == 16: four 16-bit fields in 64 bits) instead of a
+    // gathered here once per tile (four 16-bit fields in 64 bits) instead of a
     // wave OR-reduction of the lanes' masks in every round
     uint32_t hu_lo = 0, hu_hi = 0;
     for (uint64_t a = (uint64_t)a_lo + lane;; a += 64) {
@@ -461,41 +561,31 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
                 in = true;
                 const uint32_t bit = (uint32_t)(off - g0);
                 twice = (atomicOr(&hmask[bit >> 5], 1u << (bit & 31)) >> (bit & 31)) & 1u;
-                if (kLaneOps == 16 && kRounds <= 4) {
-                    const uint32_t f = ((bit / kRoundOps) & 1u) * 16u + (bit & 15u);
-                    if ((bit / kRoundOps) & 2u) hu_hi |= 1u << f; else hu_lo |= 1u << f;
-                }
+                const uint32_t f = ((bit / kRoundOps) & 1u) * 16u + (bit & 15u);
+                if ((bit / kRoundOps) & 2u) hu_hi |= 1u << f; else hu_lo |= 1u << f;
             }
         }
         dup = dup || __any(twice);
         if (!__all(in)) break;
     }
-    if (kLaneOps == 16 && kRounds <= 4) {
-        hu_lo = wave_or_u32(hu_lo);
-        hu_hi = wave_or_u32(hu_hi);
-    }
+    hu_lo = wave_or_u32(hu_lo);
+    hu_hi = wave_or_u32(hu_hi);
     wave_lds_sync();
     // this lane's start bits of all rounds move to two registers; the mask's LDS then serves as the
     // per-round signature queue (1 KiB at 64 entries, 1.5 KiB at the one-round tiles' 96) — six 4-wave workgroups
     // stay on a CU either way
-    static_assert(kLaneOps == 16 && kRounds <= 4, "the queue aliases the start mask: 16 ops per lane, at most 4 rounds");
     constexpr int kQ = queue_cap<TILE_OPS>();
     static_assert(kQ * sizeof(uint4) <= head_words<TILE_OPS>() * sizeof(uint32_t), "queue must fit the start mask's LDS");
-    uint32_t hm01 = 0, hm23 = 0;
-    if (kLaneOps == 16 && kRounds <= 4) {
-        const uint32_t sh = ((uint32_t)lane & 1u) * 16u, wi = (uint32_t)lane >> 1;
-        const uint32_t h0 = (hmask[wi] >> sh) & 0xFFFFu;
-        const uint32_t h1 = kRounds > 1 ? (hmask[32 + wi] >> sh) & 0xFFFFu : 0u;
-        const uint32_t h2 = kRounds > 2 ? (hmask[64 + wi] >> sh) & 0xFFFFu : 0u;
-        const uint32_t h3 = kRounds > 3 ? (hmask[96 + wi] >> sh) & 0xFFFFu : 0u;
-        hm01 = h0 | (h1 << 16);
-        hm23 = h2 | (h3 << 16);
-        wave_lds_sync();
-    }
+    const uint32_t sh = ((uint32_t)lane & 1u) * 16u, wi = (uint32_t)lane >> 1;
+    const uint32_t h0 = (hmask[wi] >> sh) & 0xFFFFu, h1 = (hmask[32 + wi] >> sh) & 0xFFFFu;
+    const uint32_t h2 = (hmask[64 + wi] >> sh) & 0xFFFFu, h3 = (hmask[96 + wi] >> sh) & 0xFFFFu;
+    const uint32_t hm01 = h0 | (h1 << 16), hm23 = h2 | (h3 << 16);
+    wave_lds_sync();
 
     SVX_PROF_T(t_pro);
     SVX_PROF_ADD(0, t_pro - t_begin);
-    // ---- tile state carried across rounds (wave-uniform) ----
+    // ---- tile state carried across rounds (wave-uniform): the rounds so far as one range — the four fields of a
+    // SegCarry kept as scalars (seen = has_start, carry_r / carry_d = ref / read, tile_cnt = count) ----
     uint32_t carry_r = 0, carry_d = 0;
     bool seen = false, overflow = false;
     uint32_t tile_cnt = 0, heads_before = 0;
@@ -516,10 +606,8 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
     };
     uint32_t obase = 0;
     if (MODE == MODE_DIRECT) {
-        carry_r = in.carry_r;
-        carry_d = in.carry_d;
-        seen = true;  // carry-in already holds "since the last start before the tile"
-        obase = in.obase;
+        carry_r = in.before.ref; carry_d = in.before.read; seen = true;
+        obase = in.before.count;
     }
 
     for (int round = 0; round < kRounds; ++round) {
@@ -527,9 +615,6 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
         if (ro >= tile_len) break;  // wave-uniform
 
         SVX_PROF_T(t_r0);
-        // ---- transpose through wave-private LDS.  uint4 #i (= lane's k-th load) belongs to lane
-        // c = i / kLU as its p = i % kLU -th group; it is stored at c*kLU + (p ^ xswz(c)), which keeps
-        // both the ds_write_b128 and the per-group ds_read_b128 bank-conflict free ----
         // every length of the round below 2^24 (any real CIGAR): the walk may use 24-bit multiply-adds
         bool fast24 = false;
         if (!SOA) {
@@ -539,65 +624,34 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
             fast24 = __builtin_amdgcn_ballot_w64((any >> 28) != 0u) == 0ull;
         }
 #pragma unroll
-        for (int k = 0; k < kLU; ++k) {
-            const int i = k * 64 + lane;
-            const int c = i / kLU;
-            xp[c * kLU + ((i & (kLU - 1)) ^ xswz(c))] = q[k];
-        }
+        for (int k = 0; k < kLU; ++k) xp[xpose_slot(k * 64 + lane)] = q[k];
         uint32_t opw[kLU];
 #pragma unroll
         for (int k = 0; k < kLU; ++k) opw[k] = qo[k];
         // software pipeline: next round's global loads are in flight during this round's math
         if (round + 1 < kRounds && ro + kRoundOps < tile_len)
-            load_round<SOA>(rs_c, rs_o, tile_len, ro + kRoundOps, lane, q, qo);
+            load_round<SOA>(ts.rs_c, ts.rs_o, tile_len, ro + kRoundOps, lane, q, qo);
         wave_lds_sync();
         SVX_PROF_T(t_r1);
         SVX_PROF_ADD(1, t_r1 - t_r0);  // wait for the round's data + transpose
         const uint32_t lbase = round * kRoundOps + lane * kLaneOps;  // tile-local index of op 0
-        const uint32_t hm = (kLaneOps == 16 && kRounds <= 4)
-                                ? (((round & 2) ? hm23 : hm01) >> ((round & 1) * 16)) & 0xFFFFu
-                                : (kLaneOps == 32 ? hmask[lbase >> 5]
-                                                  : (hmask[lbase >> 5] >> (lbase & 31)) & ((1u << (kLaneOps & 31)) - 1u));
+        const uint32_t hm = (((round & 2) ? hm23 : hm01) >> ((round & 1) * 16)) & 0xFFFFu;
         // slots where ANY lane starts an alignment (SGPR)
-        const uint32_t HU = (kLaneOps == 16 && kRounds <= 4) ? (((round & 2) ? hu_hi : hu_lo) >> ((round & 1) * 16)) & 0xFFFFu
-                                                              : wave_or_u32(hm);
+        const uint32_t HU = (((round & 2) ? hu_hi : hu_lo) >> ((round & 1) * 16)) & 0xFFFFu;
         const uint4* myx = xp + lane * kLU;   // this lane's consecutive ops, 4 per uint4 (swizzled)
         const int swz = xswz(lane);
 
-        DirectCtx dc;
-        dc.in_r = 0; dc.in_d = 0; dc.out0 = 0; dc.a_lo = a_lo; dc.g_lane0 = g0 + lbase;
-        dc.aln0 = 0; dc.rs0 = 0; dc.dup = dup;
+        DirectCtx dc = direct_ctx(a_lo, g0 + lbase, dup);
         constexpr int kWalk1 = (MODE == MODE_STAGE) ? WALK_QUEUE : WALK_TOTALS;
         const WalkOut wo = (!SOA && fast24) ? walk16<kWalk1, SOA, !SOA, kQ>(p, myx, swz, opw, hm, HU, lane, queue, dc)
                                             : walk16<kWalk1, SOA, false, kQ>(p, myx, swz, opw, hm, HU, lane, queue, dc);
 
         SVX_PROF_T(t_r2);
         SVX_PROF_ADD(2, t_r2 - t_r1);  // walk
-        // ---- wave scans (DPP).  Plain inclusive sums of the lane totals, signature counts and
-        // alignment-start counts; the segmentation is applied afterwards: the carry-in of lane l is
-        // its exclusive sum plus Q(h) = tail(h) - P(h) of the last lane h < l that holds an
-        // alignment start (ballot + one ds_bpermute per cursor), or plus the round's carry. ----
-        uint32_t pr = wo.tot_r, pd = wo.tot_d, sc = wo.n_emit | ((uint32_t)__popc(hm) << 16);
-#define SVX_ADD3_STEP(CTRL, RM) \
-        pr += dpp0<CTRL, RM>(pr); pd += dpp0<CTRL, RM>(pd); sc += dpp0<CTRL, RM>(sc);
-        SVX_ADD3_STEP(kDppShr1, 0xF) SVX_ADD3_STEP(kDppShr2, 0xF) SVX_ADD3_STEP(kDppShr4, 0xF)
-        SVX_ADD3_STEP(kDppShr8, 0xF) SVX_ADD3_STEP(kDppBcast15, 0xA) SVX_ADD3_STEP(kDppBcast31, 0xC)
-#undef SVX_ADD3_STEP
-        // sc packs two counters: signatures (low 16 bits, <= 1024) and alignment starts (high 16 bits)
-        const uint32_t xr = dpp0<kDppWaveShr1, 0xF>(pr), xd = dpp0<kDppWaveShr1, 0xF>(pd),
-                       xch = dpp0<kDppWaveShr1, 0xF>(sc);
-        const uint32_t xc = xch & 0xFFFFu;
-        const uint32_t CH = __builtin_amdgcn_readlane(sc, 63);
-        const uint32_t C = CH & 0xFFFFu;
-        const uint64_t H = __builtin_amdgcn_ballot_w64(hm != 0);
-        const uint64_t hl = H & ((1ull << lane) - 1ull);
-        const uint32_t qr = wo.tail_r - pr, qd = wo.tail_d - pd;
-        const bool xf = hl != 0;  // a start in an earlier lane of this round
-        const int hsrc = xf ? 63 - __clzll((long long)hl) : 0;
-        const uint32_t gq_r = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)qr);
-        const uint32_t gq_d = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)qd);
-        const uint32_t in_r = xr + (xf ? gq_r : carry_r);   // lane carry-in
-        const uint32_t in_d = xd + (xf ? gq_d : carry_d);
+        RoundScan rs;
+        round_scan(rs, wo, hm, lane);
+        const uint32_t in_r = rs.in_r(carry_r), in_d = rs.in_d(carry_d);
+        const uint32_t C = rs.total & 0xFFFFu;
 
         if (MODE == MODE_STAGE) {
             if (C) {  // wave-uniform
@@ -607,7 +661,7 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
                 }
                 // .z: signatures before this lane | alignment starts before this lane in the round << 12
                 //     | "still lacks the tile's carry-in" << 31;   .w: this lane's start mask
-                lcarry[lane] = make_uint4(in_r, in_d, xc | ((xch >> 16) << 12) | ((!seen && !xf) ? 0x80000000u : 0u), hm);
+                lcarry[lane] = make_uint4(in_r, in_d, rs.xc | (rs.xh << 12) | ((!seen && !rs.xf) ? 0x80000000u : 0u), hm);
                 wave_lds_sync();
                 const uint32_t n_here = wo.n_queued < (uint32_t)kQ ? wo.n_queued : (uint32_t)kQ;
                 for (uint32_t qb = 0; qb < n_here; qb += 64u)  // (a second pass only for a round with more than 64)
@@ -637,13 +691,7 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
             }
         } else {
             if (C) {  // dense tile: second walk finishes each signature on the spot
-                dc.in_r = in_r; dc.in_d = in_d;
-                dc.out0 = (uint64_t)obase + tile_cnt + xc;
-                // the alignment the lane's first op continues: a_lo - 1 + the starts before the lane inside the tile
-                // (none before the batch's first op: that op is a start itself)
-                dc.aln0 = !dup ? a_lo + heads_before + (xch >> 16) - 1u
-                               : (dc.g_lane0 ? find_aln(p.aln_off, p.n_aln, a_lo, dc.g_lane0 - 1u) : 0xFFFFFFFFu);
-                dc.rs0 = (p.ref_start && dc.aln0 < p.n_aln) ? (uint32_t)p.ref_start[dc.aln0] : 0u;
+                direct_fill(p, dc, rs, SegCarry{1u, carry_r, carry_d, obase + tile_cnt}, heads_before);
                 (void)walk16<WALK_DIRECT, SOA, false>(p, myx, swz, opw, hm, HU, lane, queue, dc);
             }
         }
@@ -651,19 +699,20 @@ __device__ __forceinline__ uint4 process_tile(const CigarArgs& p, const uint32_t
         SVX_PROF_T(t_r3);
         SVX_PROF_ADD(3, t_r3 - t_r2);  // scans + flush
 
-        // ---- carry to the next round (wave-uniform) ----
-        const uint32_t R = __builtin_amdgcn_readlane(pr, 63), D = __builtin_amdgcn_readlane(pd, 63);
-        if (H) {
-            const int hlast = 63 - __clzll((long long)H);
-            carry_r = R + __builtin_amdgcn_readlane(qr, hlast);
-            carry_d = D + __builtin_amdgcn_readlane(qd, hlast);
+        // ---- carry to the next round (wave-uniform): OpSeg()(round_carry(rs), carry) on the four scalars, as a branch —
+        // the streaming kernels are four instructions and one schedule away from this form with the operator ----
+        const uint32_t R = __builtin_amdgcn_readlane(rs.incl.r, 63), D = __builtin_amdgcn_readlane(rs.incl.d, 63);
+        if (rs.H) {
+            const int hlast = 63 - __clzll((long long)rs.H);
+            carry_r = R + __builtin_amdgcn_readlane(rs.qr, hlast);
+            carry_d = D + __builtin_amdgcn_readlane(rs.qd, hlast);
             seen = true;
         } else {
             carry_r += R;
             carry_d += D;
         }
         tile_cnt += C;
-        heads_before += CH >> 16;
+        heads_before += rs.total >> 16;
     }
 
 #ifdef SVX_EXP_PROF
@@ -694,15 +743,17 @@ __device__ __forceinline__ void fold_group_desc(const CigarArgs& p, uint4* s_agg
     if (lane == 0) s_agg[wave] = dsc;
     __syncthreads();
     if (threadIdx.x == 0) {
+        // OpSeg()(desc_carry(v), {f, r, d, c}) and desc_dense(v), written out: this is the tail of the one-round tile
+        // kernels, and through the two helpers its scalar code comes out in another order and polarity
         uint32_t f = 0, r = 0, d = 0, c = 0, dense = 0;
 #pragma unroll
         for (int k = 0; k < kWaves; ++k) {
             const uint4 v = s_agg[k];
             if (v.x >> 31) { f = 1; r = v.y; d = v.z; }
             else { r += v.y; d += v.z; }
-            c += v.x & 0x3FFFFFFFu;
+            c += v.x & kDescCount;
             // .w: which of the four tiles k_cigar_finish_small has to walk again (beyond the slab, or a round beyond the queue)
-            if ((v.x & 0x3FFFFFFFu) > (uint32_t)kSlab || (v.x & kDescForceDense)) dense |= 1u << k;
+            if ((v.x & kDescCount) > (uint32_t)kSlab || (v.x & kDescForceDense)) dense |= 1u << k;
         }
         p.desc4[group] = make_uint4(c | (f << 31), r, d, dense);
     }
@@ -770,18 +821,20 @@ __global__ __launch_bounds__(kScanBlock) void k_desc_scan(const uint4* __restric
     const uint32_t n_blocks = gridDim.x;
     {
         const uint32_t t = blockIdx.x * kScanBlock + tid;
-        uint32_t f = 0, sr = 0, sd = 0, sc = 0;
+        SegCarry v{0u, 0u, 0u, 0u};
         if (t < n_tiles) {
-            const uint4 v = desc[t];
-            sc = v.x & 0x3FFFFFFFu;
-            f = v.x >> 31;
-            sr = v.y;
-            sd = v.z;
-            if (sc > (uint32_t)kSlab || (v.x & kDescForceDense)) dense_list[atomicAdd(n_dense, 1u)] = t;
+            const uint4 d = desc[t];
+            v = desc_carry(d);
+            if (desc_dense(d)) dense_list[atomicAdd(n_dense, 1u)] = t;
         }
-        SVX_SEG_SCAN()
+        v = wave_scan(v, OpSeg());
+        const uint32_t f = v.has_start, sr = v.ref, sd = v.read, sc = v.count;
         if (lane == 63) { s_f[wave] = f; s_r[wave] = sr; s_d[wave] = sd; s_c[wave] = sc; }
         __syncthreads();
+        // The fold across the waves is OpSeg on scalars out of four LDS arrays, here, in the second scan below and in
+        // k_cigar_finish_small.  (svx_scan_dev.h's group_before combines (front, later) and is for four waves; a helper
+        // over an array of SegCarry in LDS cost this kernel 0.4 us of 6.1 and either 54 more VGPRs or a partly rolled
+        // loop: profiles/cigar_one_scan_refactor.txt.)
         uint32_t pf = 0, pr_ = 0, pd_ = 0, pc = 0;  // prefix over preceding waves
         uint32_t af = 0, ar = 0, ad = 0, ac = 0;    // aggregate over all waves
         for (int w2 = 0; w2 < kScanBlock / 64; ++w2) {
@@ -790,8 +843,8 @@ __global__ __launch_bounds__(kScanBlock) void k_desc_scan(const uint4* __restric
             else { ar += s_r[w2]; ad += s_d[w2]; }
             ac += s_c[w2];
         }
-        const uint32_t xf = dpp0<kDppWaveShr1, 0xF>(f), xr = dpp0<kDppWaveShr1, 0xF>(sr),
-                       xd = dpp0<kDppWaveShr1, 0xF>(sd), xc = dpp0<kDppWaveShr1, 0xF>(sc);
+        const SegCarry x = lane_before(v);
+        const uint32_t xf = x.has_start, xr = x.ref, xd = x.read, xc = x.count;
         if (t < n_tiles) {
             carry_ref[t] = xf ? xr : pr_ + xr;
             carry_read[t] = xf ? xd : pd_ + xd;
@@ -816,12 +869,13 @@ __global__ __launch_bounds__(kScanBlock) void k_desc_scan(const uint4* __restric
     uint64_t cc = 0;
     for (uint32_t base = 0; base < n_blocks; base += kScanBlock) {
         const uint32_t b = base + tid;
-        uint32_t f = 0, sr = 0, sd = 0, sc = 0;
+        SegCarry v{0u, 0u, 0u, 0u};
         if (b < n_blocks) {
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(blk_agg, n_blocks * 16u), (int)(b * 16u), 0, 17);
-            f = v.x; sr = v.y; sd = v.z; sc = v.w;
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(blk_agg, n_blocks * 16u), (int)(b * 16u), 0, 17);
+            v = SegCarry{w.x, w.y, w.z, w.w};
         }
-        SVX_SEG_SCAN()
+        v = wave_scan(v, OpSeg());
+        const uint32_t f = v.has_start, sr = v.ref, sd = v.read, sc = v.count;
         __syncthreads();
         if (lane == 63) { s_f[wave] = f; s_r[wave] = sr; s_d[wave] = sd; s_c[wave] = sc; }
         __syncthreads();
@@ -835,8 +889,8 @@ __global__ __launch_bounds__(kScanBlock) void k_desc_scan(const uint4* __restric
             else { ar += s_r[w2]; ad += s_d[w2]; }
             ac += s_c[w2];
         }
-        const uint32_t xf = dpp0<kDppWaveShr1, 0xF>(f), xr = dpp0<kDppWaveShr1, 0xF>(sr),
-                       xd = dpp0<kDppWaveShr1, 0xF>(sd), xc = dpp0<kDppWaveShr1, 0xF>(sc);
+        const SegCarry x = lane_before(v);
+        const uint32_t xf = x.has_start, xr = x.ref, xd = x.read, xc = x.count;
         if (b < n_blocks)
             blk_prefix[b] = make_uint4(xf | pf, xf ? xr : pr_ + xr, xf ? xd : pd_ + xd, (uint32_t)(pc + xc));
         cf = af; cr = ar; cd = ad; cc = ac;
@@ -858,25 +912,21 @@ constexpr int kFinLanes = 16;
 #define SVX_FINSPEC 3
 #endif
 constexpr int kFinSpec = SVX_FINSPEC;  // records per lane requested together with the descriptor (48 per tile)
-__device__ __forceinline__ void cigar_finish_block(const CigarArgs& p, const uint32_t block) {
-    const uint32_t tile = block * (256u / kFinLanes) + threadIdx.x / kFinLanes;
-    const uint32_t l = threadIdx.x % kFinLanes;
-    if (tile >= p.n_tiles) return;
-    // speculative: slots past the tile's count hold stale bytes and are never used
-    uint4 spec[kFinSpec];
+// a lane's first kFinSpec records of a tile's slab (zeros for a lane without a tile).  Speculative: slots past the
+// tile's count hold stale bytes and are never used
+__device__ __forceinline__ void load_spec(const CigarArgs& p, const bool mine, const uint32_t tile, const uint32_t l,
+                                          uint4 (&spec)[kFinSpec]) {
 #pragma unroll
-    for (int k = 0; k < kFinSpec; ++k) spec[k] = p.slab[(uint64_t)tile * kSlab + l + k * kFinLanes];
-    const uint4 dsc = p.desc[tile];
-    const uint4 bp = p.blk_prefix[tile / kScanBlock];
-    const uint32_t lb = p.out_base[tile];
-    const uint32_t lcr = p.carry_ref[tile], lcd = p.carry_read[tile];
-    const uint32_t cnt = dsc.x & 0x3FFFFFFFu;
-    if (cnt == 0 || cnt > (uint32_t)kSlab || (dsc.x & kDescForceDense)) return;  // dense: k_cigar_dense
-    const bool local_head = (lb >> 31) != 0;
-    const uint32_t cr = lcr + (local_head ? 0u : bp.y);
-    const uint32_t cd = lcd + (local_head ? 0u : bp.z);
-    const uint64_t ob = (uint64_t)(lb & 0x7FFFFFFFu) + bp.w;
-    // the ref_start gathers of both speculative records go out together
+    for (int k = 0; k < kFinSpec; ++k)
+        spec[k] = mine ? p.slab[(uint64_t)tile * kSlab + l + k * kFinLanes] : make_uint4(0, 0, 0, 0);
+}
+
+// Lane l of the 16 that finish a sparse tile: its `cnt` slab records become rows out_base .. of the final SoA, plus the
+// tile's carry-in where a record precedes the tile's first alignment start, plus ref_start of the record's alignment.
+__device__ __forceinline__ void finish_records(const CigarArgs& p, const uint32_t tile, const uint32_t l, const uint32_t cnt,
+                                               const uint4 (&spec)[kFinSpec], const uint32_t carry_ref,
+                                               const uint32_t carry_read, const uint64_t out_base) {
+    // the ref_start gathers of all speculative records go out together
     uint32_t rs[kFinSpec];
 #pragma unroll
     for (int k = 0; k < kFinSpec; ++k)
@@ -884,21 +934,43 @@ __device__ __forceinline__ void cigar_finish_block(const CigarArgs& p, const uin
 #pragma unroll
     for (int k = 0; k < kFinSpec; ++k) {
         const uint32_t r = l + k * kFinLanes;
-        if (r < cnt && ob + r < p.cap) {
+        if (r < cnt && out_base + r < p.cap) {
             const uint4 rec = spec[k];
             const uint32_t len = rec.w & 0x0FFFFFFFu, type = (rec.w >> 28) & 1u, prec = (rec.w >> 29) & 1u;
-            p.out.aln[ob + r] = rec.x;
-            p.out.ref_pos[ob + r] = rec.y + (prec ? cr : 0u) + rs[k];
-            p.out.read_pos[ob + r] = rec.z + (prec ? cd : 0u);
-            p.out.len[ob + r] = len;
-            p.out.type[ob + r] = (uint8_t)type;
+            p.out.aln[out_base + r] = rec.x;
+            p.out.ref_pos[out_base + r] = rec.y + (prec ? carry_ref : 0u) + rs[k];
+            p.out.read_pos[out_base + r] = rec.z + (prec ? carry_read : 0u);
+            p.out.len[out_base + r] = len;
+            p.out.type[out_base + r] = (uint8_t)type;
         }
     }
     for (uint32_t r = l + kFinSpec * kFinLanes; r < cnt; r += kFinLanes) {
         const uint4 rec = p.slab[(uint64_t)tile * kSlab + r];
         const uint32_t len = rec.w & 0x0FFFFFFFu, type = (rec.w >> 28) & 1u, prec = (rec.w >> 29) & 1u;
-        store_final(p, ob + r, rec.x, rec.y + (prec ? cr : 0u), rec.z + (prec ? cd : 0u), len, type);
+        store_final(p, out_base + r, rec.x, rec.y + (prec ? carry_ref : 0u), rec.z + (prec ? carry_read : 0u), len, type);
     }
+}
+
+// The range in front of a tile, rebuilt from k_desc_scan's outputs: the tile's prefix inside its scan block (out_base bit
+// 31 = a start precedes the tile inside the block: the local carry is complete) behind the block's prefix.  .count is
+// the tile's output base.
+__device__ __forceinline__ SegCarry tile_before(const CigarArgs& p, const uint32_t tile) {
+    const uint4 bp = p.blk_prefix[tile / kScanBlock];
+    const uint32_t lb = p.out_base[tile];
+    return OpSeg()(SegCarry{lb >> 31, p.carry_ref[tile], p.carry_read[tile], lb & 0x7FFFFFFFu}, SegCarry{bp.x, bp.y, bp.z, bp.w});
+}
+
+__device__ __forceinline__ void cigar_finish_block(const CigarArgs& p, const uint32_t block) {
+    const uint32_t tile = block * (256u / kFinLanes) + threadIdx.x / kFinLanes;
+    const uint32_t l = threadIdx.x % kFinLanes;
+    if (tile >= p.n_tiles) return;
+    uint4 spec[kFinSpec];
+    load_spec(p, true, tile, l, spec);
+    const uint4 dsc = p.desc[tile];
+    const SegCarry before = tile_before(p, tile);
+    const uint32_t cnt = dsc.x & kDescCount;
+    if (cnt == 0 || desc_dense(dsc)) return;  // dense: k_cigar_dense
+    finish_records(p, tile, l, cnt, spec, before.ref, before.read, before.count);
 }
 
 __global__ __launch_bounds__(256) void k_cigar_finish(CigarArgs p) { cigar_finish_block(p, blockIdx.x); }
@@ -911,25 +983,21 @@ __global__ __launch_bounds__(256) void k_cigar_finish(CigarArgs p) { cigar_finis
 // and emit side by side.  (Round 3 gave a tile to one wave, which walked the rounds one after the other and
 // searched aln_off once per signature: 25 us per tile, 73 us for the product's full-size sample.) ----
 struct RoundTotals {
-    uint32_t r, d, tail_r, tail_d, cnt, heads, seen, pad;
+    SegCarry c;  // the round as one range
+    uint32_t heads;
 };
 
 template <bool SOA>
 __device__ __forceinline__ void dense_tile_wg(const CigarArgs& p, const uint32_t tile, const int wave, const int lane,
                                               uint4* xp, uint32_t* hmask, uint32_t* s_dup, RoundTotals* s_round,
                                               const TileIn& in) {
-    static_assert(kRounds == kWaves && kLaneOps == 16, "one wave per round");
-    const uint64_t g0 = (uint64_t)tile * kTileOps;
-    const uint64_t tile_end = (g0 + kTileOps < p.n_ops) ? g0 + kTileOps : p.n_ops;
-    const uint32_t tile_len = (uint32_t)(tile_end - g0);
+    static_assert(kRounds == kWaves, "one wave per round");
+    const TileSpan ts = tile_span<SOA, kTileOps>(p, tile);
     const uint32_t ro = (uint32_t)wave * kRoundOps;
-    const bool live = ro < tile_len;  // wave-uniform: the ragged last tile may not reach this wave's round
-    const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(p.cigar + g0, tile_len * 4u);
-    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(SOA ? (const void*)(p.op + g0) : (const void*)p.cigar,
-                                                  SOA ? ((tile_len + 3u) & ~3u) : 0u);
+    const bool live = ro < ts.len;  // wave-uniform: the ragged last tile may not reach this wave's round
     uint4 q[kLU];
     uint32_t qo[kLU] = {};
-    if (live) load_round<SOA>(rs_c, rs_o, tile_len, ro, lane, q, qo);
+    if (live) load_round<SOA>(ts.rs_c, ts.rs_o, ts.len, ro, lane, q, qo);
     // ---- the tile's start mask, built by the whole workgroup
     const int tid = wave * 64 + lane;
     if (tid < kTileOps / 32) hmask[tid] = 0;
@@ -939,9 +1007,9 @@ __device__ __forceinline__ void dense_tile_wg(const CigarArgs& p, const uint32_t
         bool inside = false;
         if (a < p.n_aln) {
             const uint64_t off = p.aln_off[a];
-            if (off < tile_end) {
+            if (off < ts.end) {
                 inside = true;
-                const uint32_t bit = (uint32_t)(off - g0);
+                const uint32_t bit = (uint32_t)(off - ts.g0);
                 if ((atomicOr(&hmask[bit >> 5], 1u << (bit & 31)) >> (bit & 31)) & 1u) *s_dup = 1u;
             }
         }
@@ -952,66 +1020,34 @@ __device__ __forceinline__ void dense_tile_wg(const CigarArgs& p, const uint32_t
     const uint32_t lbase = ro + (uint32_t)lane * kLaneOps;
     const uint32_t hm = (hmask[lbase >> 5] >> (lbase & 31)) & 0xFFFFu;
     const uint32_t HU = wave_or_u32(hm);
-    uint32_t pr = 0, pd = 0, sc = 0, qr = 0, qd = 0;
-    uint64_t H = 0;
     uint32_t opw[kLU];
 #pragma unroll
     for (int k = 0; k < kLU; ++k) opw[k] = qo[k];
     const uint4* myx = xp + lane * kLU;
     const int swz = xswz(lane);
-    DirectCtx dc;
-    dc.in_r = 0; dc.in_d = 0; dc.out0 = 0; dc.a_lo = in.a_lo; dc.g_lane0 = g0 + lbase; dc.aln0 = 0; dc.rs0 = 0; dc.dup = dup;
+    DirectCtx dc = direct_ctx(in.a_lo, ts.g0 + lbase, dup);
+    RoundScan rs{};  // (a round behind the tile's end: nothing)
     if (live) {
 #pragma unroll
-        for (int k = 0; k < kLU; ++k) {
-            const int i = k * 64 + lane;
-            const int c = i / kLU;
-            xp[c * kLU + ((i & (kLU - 1)) ^ xswz(c))] = q[k];
-        }
+        for (int k = 0; k < kLU; ++k) xp[xpose_slot(k * 64 + lane)] = q[k];
         wave_lds_sync();
-        const WalkOut wo = walk16<WALK_TOTALS, SOA, false>(p, myx, swz, opw, hm, HU, lane, nullptr, dc);
-        pr = wo.tot_r; pd = wo.tot_d; sc = wo.n_emit | ((uint32_t)__popc(hm) << 16);
-#define SVX_ADD3_STEP(CTRL, RM) \
-        pr += dpp0<CTRL, RM>(pr); pd += dpp0<CTRL, RM>(pd); sc += dpp0<CTRL, RM>(sc);
-        SVX_ADD3_STEP(kDppShr1, 0xF) SVX_ADD3_STEP(kDppShr2, 0xF) SVX_ADD3_STEP(kDppShr4, 0xF)
-        SVX_ADD3_STEP(kDppShr8, 0xF) SVX_ADD3_STEP(kDppBcast15, 0xA) SVX_ADD3_STEP(kDppBcast31, 0xC)
-#undef SVX_ADD3_STEP
-        H = __builtin_amdgcn_ballot_w64(hm != 0);
-        qr = wo.tail_r - pr; qd = wo.tail_d - pd;
+        round_scan(rs, walk16<WALK_TOTALS, SOA, false>(p, myx, swz, opw, hm, HU, lane, nullptr, dc), hm, lane);
     }
-    if (lane == 0) {
-        RoundTotals t;
-        const uint32_t R = __builtin_amdgcn_readlane(pr, 63), D = __builtin_amdgcn_readlane(pd, 63);
-        const uint32_t CH = __builtin_amdgcn_readlane(sc, 63);
-        const int hlast = H ? 63 - __clzll((long long)H) : 0;
-        t.r = R; t.d = D; t.cnt = CH & 0xFFFFu; t.heads = CH >> 16; t.seen = H ? 1u : 0u; t.pad = 0;
-        t.tail_r = R + __builtin_amdgcn_readlane(qr, hlast);
-        t.tail_d = D + __builtin_amdgcn_readlane(qd, hlast);
-        s_round[wave] = t;
-    }
+    const SegCarry rc = round_carry(rs);
+    if (lane == 0) s_round[wave] = RoundTotals{rc, rs.total >> 16};
     __syncthreads();
     // ---- carry into this wave's round: fold the rounds before it (wave-uniform scalars)
-    uint32_t carry_r = in.carry_r, carry_d = in.carry_d, cnt_before = 0, heads_before = 0;
-    for (int k = 0; k < wave; ++k) {
-        const RoundTotals t = s_round[k];
-        if (t.seen) { carry_r = t.tail_r; carry_d = t.tail_d; }
-        else { carry_r += t.r; carry_d += t.d; }
-        cnt_before += t.cnt;
-        heads_before += t.heads;
-    }
-    if (live && (__builtin_amdgcn_readlane(sc, 63) & 0xFFFFu)) {
-        const uint32_t xr = dpp0<kDppWaveShr1, 0xF>(pr), xd = dpp0<kDppWaveShr1, 0xF>(pd), xch = dpp0<kDppWaveShr1, 0xF>(sc);
-        const uint64_t hl = H & ((1ull << lane) - 1ull);
-        const bool xf = hl != 0;
-        const int hsrc = xf ? 63 - __clzll((long long)hl) : 0;
-        const uint32_t gq_r = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)qr);
-        const uint32_t gq_d = (uint32_t)__builtin_amdgcn_ds_bpermute(hsrc << 2, (int)qd);
-        dc.in_r = xr + (xf ? gq_r : carry_r);
-        dc.in_d = xd + (xf ? gq_d : carry_d);
-        dc.out0 = (uint64_t)in.obase + cnt_before + (xch & 0xFFFFu);
-        dc.aln0 = !dup ? in.a_lo + heads_before + (xch >> 16) - 1u
-                       : (dc.g_lane0 ? find_aln(p.aln_off, p.n_aln, in.a_lo, dc.g_lane0 - 1u) : 0xFFFFFFFFu);
-        dc.rs0 = (p.ref_start && dc.aln0 < p.n_aln) ? (uint32_t)p.ref_start[dc.aln0] : 0u;
+    SegCarry before = in.before;  // .count: output slot of the round's first signature
+    uint32_t heads_before = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves - 1; ++k)
+        if (k < wave) {
+            const RoundTotals t = s_round[k];
+            before = OpSeg()(t.c, before);
+            heads_before += t.heads;
+        }
+    if (live && rc.count) {
+        direct_fill(p, dc, rs, before, heads_before);
         (void)walk16<WALK_DIRECT, SOA, false>(p, myx, swz, opw, hm, HU, lane, nullptr, dc);
     }
     __syncthreads();  // the mask, the totals and the transpose buffers are rewritten for the next tile
@@ -1200,9 +1236,6 @@ enum { A3_ROWS_TREE = 1, A3_POST = 2 };
 #ifndef SVX_CHUNK_X4
 #define SVX_CHUNK_X4 2
 #endif
-#ifndef SVX_A3_NT
-#define SVX_A3_NT 0
-#endif
 constexpr int kChunkX4 = SVX_CHUNK_X4;       // 16-byte loads per lane and step
 constexpr int kChunkOps = 64 * kChunkX4;     // 16 lanes x 4 words x kChunkX4 = 128
 // (Round 4: one word per load, 14 VALU per word, a materialised chunk list in LDS and alignments beyond 2048 ops walked
@@ -1227,9 +1260,7 @@ __device__ __forceinline__ uint32_t row16_sum(uint32_t v) {
 }
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += dpp0<kDppShr1, 0xF>(v); v += dpp0<kDppShr2, 0xF>(v); v += dpp0<kDppShr4, 0xF>(v); v += dpp0<kDppShr8, 0xF>(v);
-    v += dpp0<kDppBcast15, 0xA>(v); v += dpp0<kDppBcast31, 0xC>(v);
-    return v;
+    return wave_scan(v, OpAdd32());
 }
 
 // four consecutive CIGAR words at any word address (a global 16-byte load only needs dword alignment)
@@ -1307,11 +1338,7 @@ __device__ __forceinline__ void a3_chain_block(const A3Args& a, const uint32_t b
             }
             __syncthreads();
             {
-#ifdef SVX_EXP_A3_NOCHUNK  // timing ablation: wrong rows
-                const uint32_t total = 0;
-#else
                 const uint32_t total = lds->cpre[256];
-#endif
                 const uint32_t per_group = (total + 15u) / 16u;
                 const uint32_t c_lo = (uint32_t)gid * per_group < total ? (uint32_t)gid * per_group : total;
                 const uint32_t c_hi = c_lo + per_group < total ? c_lo + per_group : total;
@@ -1358,11 +1385,7 @@ __device__ __forceinline__ void a3_chain_block(const A3Args& a, const uint32_t b
                             if (rel < nv) {
                                 const uint32_t rem = nv - rel;
                                 if (rem >= 4u) {
-#if SVX_A3_NT
-                                    const u32x4_dw v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_dw*>(src + rel));
-#else
                                     const u32x4_dw v = *reinterpret_cast<const u32x4_dw*>(src + rel);
-#endif
                                     w[k][0] = v.x; w[k][1] = v.y; w[k][2] = v.z; w[k][3] = v.w;
                                 } else {  // the alignment's last words (nothing behind them is read)
                                     w[k][0] = src[rel];
@@ -1446,9 +1469,6 @@ __device__ __forceinline__ void a3_chain_block(const A3Args& a, const uint32_t b
         }
         __syncthreads();
         // ---- decision tree: eight lanes per read
-#ifdef SVX_EXP_A3_NOTREE
-        return;
-#endif
         const int tl = lane & (svx_seg_dev::kGroup - 1), gbase = lane & ~(svx_seg_dev::kGroup - 1);
         for (uint32_t r0 = r_lo; r0 < r_hi; r0 += 256 / svx_seg_dev::kGroup) {
             const uint32_t r = r0 + tid / svx_seg_dev::kGroup;
@@ -1479,14 +1499,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_cigar_dense(CigarArgs p, A3Args
     const uint32_t first = WITH_POST ? n_a3_blocks : 0u;
     for (uint32_t work = blockIdx.x - first; work < n_dense; work += gridDim.x - first) {
         const uint32_t tile = p.dense_list[work];
-        const uint4 bp = p.blk_prefix[tile / kScanBlock];
-        const uint32_t lr = p.carry_ref[tile], ld = p.carry_read[tile], lb = p.out_base[tile];
-        const bool local_head = (lb >> 31) != 0;  // a start precedes the tile inside its scan block
-        TileIn in;
-        in.a_lo = p.tile_alo[tile];
-        in.carry_r = local_head ? lr : lr + bp.y;
-        in.carry_d = local_head ? ld : ld + bp.z;
-        in.obase = (lb & 0x7FFFFFFFu) + bp.w;
+        const TileIn in{p.tile_alo[tile], tile_before(p, tile)};
         dense_tile_wg<SOA>(p, tile, wave, lane, s_xpose[wave], s_mask, &s_dup, s_round, in);
     }
 }
@@ -1532,9 +1545,7 @@ __global__ __launch_bounds__(256) void k_cigar_finish_small(CigarArgs p, uint64_
     const uint32_t l = tid % kFinLanes;
     const bool mine = (uint32_t)tid < kFinTiles * kFinLanes && tile < p.n_tiles;
     uint4 spec[kFinSpec];
-#pragma unroll
-    for (int k = 0; k < kFinSpec; ++k)
-        spec[k] = mine ? p.slab[(uint64_t)tile * kSlab + l + k * kFinLanes] : make_uint4(0, 0, 0, 0);
+    load_spec(p, mine, tile, l, spec);
     const uint4 dsc = mine ? p.desc[tile] : make_uint4(0, 0, 0, 0);
 
     // ---- segmented exclusive scan over the folded descriptors of ALL groups (one per four tiles, written by the
@@ -1555,9 +1566,12 @@ __global__ __launch_bounds__(256) void k_cigar_finish_small(CigarArgs p, uint64_
         lf |= f << i;
         if (d[i].x >> 31) { f = 1; sr = d[i].y; sd = d[i].z; }
         else { sr += d[i].y; sd += d[i].z; }
-        sc += d[i].x & 0x3FFFFFFFu;
+        sc += d[i].x & kDescCount;
     }
-    SVX_SEG_SCAN()
+    {
+        const SegCarry v = wave_scan(SegCarry{f, sr, sd, sc}, OpSeg());
+        f = v.has_start; sr = v.ref; sd = v.read; sc = v.count;
+    }
     if (lane == 63) { s_f[wave] = f; s_r[wave] = sr; s_d[wave] = sd; s_c[wave] = sc; }
     if (tid == 0) s_n_dense = 0;
     __syncthreads();
@@ -1568,8 +1582,7 @@ __global__ __launch_bounds__(256) void k_cigar_finish_small(CigarArgs p, uint64_
         else { ar += s_r[w2]; ad += s_d[w2]; }
         ac += s_c[w2];
     }
-    const uint32_t xf = dpp0<kDppWaveShr1, 0xF>(f), xr = dpp0<kDppWaveShr1, 0xF>(sr),
-                   xd = dpp0<kDppWaveShr1, 0xF>(sd), xc = dpp0<kDppWaveShr1, 0xF>(sc);
+    const uint32_t xf = lane_before(f), xr = lane_before(sr), xd = lane_before(sd), xc = lane_before(sc);
     const uint32_t Tr = xf ? xr : pr_ + xr, Td = xf ? xd : pd_ + xd, Tc = pc + xc;  // exclusive over the threads before
 #pragma unroll
     for (int i = 0; i < kSmallPer; ++i) {
@@ -1606,66 +1619,30 @@ __global__ __launch_bounds__(256) void k_cigar_finish_small(CigarArgs p, uint64_
     }
     __syncthreads();
     // ---- inside the group (= this wave's four tiles, 16 lanes each): fold the tiles before mine
-    uint32_t t_cr = s_cr[wave], t_cd = s_cd[wave], t_ob = s_ob[wave];
+    SegCarry before{0u, s_cr[wave], s_cd[wave], s_ob[wave]};
     {
         const int k_mine = lane / kFinLanes;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const uint32_t vx = __builtin_amdgcn_readlane(dsc.x, k * kFinLanes), vy = __builtin_amdgcn_readlane(dsc.y, k * kFinLanes),
-                           vz = __builtin_amdgcn_readlane(dsc.z, k * kFinLanes);
-            if (k < k_mine) {
-                if (vx >> 31) { t_cr = vy; t_cd = vz; }
-                else { t_cr += vy; t_cd += vz; }
-                t_ob += vx & 0x3FFFFFFFu;
-            }
+            const uint4 v = make_uint4(__builtin_amdgcn_readlane(dsc.x, k * kFinLanes), __builtin_amdgcn_readlane(dsc.y, k * kFinLanes),
+                                       __builtin_amdgcn_readlane(dsc.z, k * kFinLanes), 0u);
+            if (k < k_mine) before = OpSeg()(desc_carry(v), before);
         }
     }
 
     // ---- finish, sparse tiles (as k_cigar_finish): 16 lanes per tile
-    const uint32_t cnt = dsc.x & 0x3FFFFFFFu;
-    const bool dense = cnt > (uint32_t)kSlab || (dsc.x & kDescForceDense);
-    if (mine && cnt && !dense) {
-        const uint32_t cr = t_cr, cd = t_cd;
-        const uint64_t ob = t_ob;
-        uint32_t rs[kFinSpec];
-#pragma unroll
-        for (int k = 0; k < kFinSpec; ++k)
-            rs[k] = (l + k * kFinLanes < cnt && p.ref_start) ? (uint32_t)p.ref_start[spec[k].x] : 0u;
-#pragma unroll
-        for (int k = 0; k < kFinSpec; ++k) {
-            const uint32_t r = l + k * kFinLanes;
-            if (r < cnt && ob + r < p.cap) {
-                const uint4 rec = spec[k];
-                const uint32_t len = rec.w & 0x0FFFFFFFu, type = (rec.w >> 28) & 1u, prec = (rec.w >> 29) & 1u;
-                p.out.aln[ob + r] = rec.x;
-                p.out.ref_pos[ob + r] = rec.y + (prec ? cr : 0u) + rs[k];
-                p.out.read_pos[ob + r] = rec.z + (prec ? cd : 0u);
-                p.out.len[ob + r] = len;
-                p.out.type[ob + r] = (uint8_t)type;
-            }
-        }
-        for (uint32_t r = l + kFinSpec * kFinLanes; r < cnt; r += kFinLanes) {
-            const uint4 rec = p.slab[(uint64_t)tile * kSlab + r];
-            const uint32_t len = rec.w & 0x0FFFFFFFu, type = (rec.w >> 28) & 1u, prec = (rec.w >> 29) & 1u;
-            store_final(p, ob + r, rec.x, rec.y + (prec ? cr : 0u), rec.z + (prec ? cd : 0u), len, type);
-        }
-    }
+    const uint32_t cnt = dsc.x & kDescCount;
+    if (mine && cnt && !desc_dense(dsc)) finish_records(p, tile, l, cnt, spec, before.ref, before.read, before.count);
     // ---- this workgroup's share of the dense tiles, one wave each, the waves taking turns: fold the tiles in front of
     // it inside its group of four (scalar loads of their descriptors), then the walk
     const uint32_t n_dense = s_n_dense;
     for (uint32_t i = wave; i < n_dense; i += kWaves) {
         const uint4 e = s_dense[i];
         TileIn in;
-        in.carry_r = e.y;
-        in.carry_d = e.z;
-        in.obase = e.w;
+        in.before = SegCarry{0u, e.y, e.z, e.w};
         const uint32_t first = e.x & ~(uint32_t)(kWaves - 1);
-        for (uint32_t t = first; t < e.x; ++t) {  // wave-uniform
-            const uint4 v = p.desc[t];
-            if (v.x >> 31) { in.carry_r = v.y; in.carry_d = v.z; }
-            else { in.carry_r += v.y; in.carry_d += v.z; }
-            in.obase += v.x & 0x3FFFFFFFu;
-        }
+        for (uint32_t t = first; t < e.x; ++t)  // wave-uniform
+            in.before = OpSeg()(desc_carry(p.desc[t]), in.before);
         in.a_lo = p.desc[e.x].w;
         (void)process_tile<MODE_DIRECT, SOA, kSmallTileOps, ALO_GIVEN>(p, e.x, lane, s_xpose[wave], s_head[wave],
                                                                               reinterpret_cast<uint4*>(s_head[wave]), nullptr, in);
@@ -1718,15 +1695,11 @@ __global__ __launch_bounds__(64 * kWaves, SVX_TILE_MIN_WAVES) void k_tiles_a3(Ci
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SVX_FIN_A3_WAVES, 8)))
 void k_finish_a3(CigarArgs p, A3Args a, uint32_t n_a3_blocks) {
     if (blockIdx.x < n_a3_blocks) {  // workgroup-uniform
-#ifndef SVX_EXP_FIN_ONLY
         __shared__ A3Lds lds;
         a3_chain_block<A3_ROWS_TREE>(a, blockIdx.x, &lds);
-#endif
         return;
     }
-#ifndef SVX_EXP_A3_ONLY
     cigar_finish_block(p, blockIdx.x - n_a3_blocks);
-#endif
 }
 
 // The CIGAR path's workspace for a batch of n_ops ops, added to `ws`: the arrays of `a`, whose n_tiles it sets; returns
@@ -1792,6 +1765,16 @@ void a3_fill(svx_takes& ws, const uint32_t* d_cigar, const uint64_t* d_aln_off, 
     a->n_deal = q.n_deal_blocks;
 }
 
+// Behind the tile launch (the dominant kernel of either path): the event svx_ctx_wait_dominant waits for, when somebody
+// pipelines against this context.
+int record_dominant(svx_ctx* ctx) {
+    if (!ctx->want_dom) return SVX_OK;
+    if (!ctx->ev_dom) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dom, hipEventDisableTiming));
+    SVX_HIP(ctx, hipEventRecord(ctx->ev_dom, ctx->stream));
+    ctx->ev_dom_recorded = true;
+    return SVX_OK;
+}
+
 // a3 != nullptr: the split-segment chain of the same submission goes out with the CIGAR path — inside the tile and
 // finish launches of the small-batch path, inside the finish and dense-tile launches of the streaming path
 // (svx_collect_batch_dev).
@@ -1855,11 +1838,7 @@ int cigar_extract_dev_impl(svx_ctx* ctx, const uint32_t* d_cigar_or_len, const u
             hipLaunchKernelGGL((k_cigar_tiles<SOA, kSmallTileOps, ALO_SEARCH>), dim3(tile_blocks), dim3(64 * kWaves), 0,
                                ctx->stream, a);
         SVX_TRY(svx_timing_mark(ctx, 2));
-        if (ctx->want_dom) {
-            if (!ctx->ev_dom) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dom, hipEventDisableTiming));
-            SVX_HIP(ctx, hipEventRecord(ctx->ev_dom, ctx->stream));
-            ctx->ev_dom_recorded = true;
-        }
+        SVX_TRY(record_dominant(ctx));
         // (at least SVX_FIN_MIN_BLOCKS workgroups: the ones beyond the tiles' own have no records to copy and only take
         //  their share of the dense tiles — a batch of a few hundred tiles that are ALL dense is a satellite array)
 #ifndef SVX_FIN_MIN_BLOCKS
@@ -1885,11 +1864,7 @@ int cigar_extract_dev_impl(svx_ctx* ctx, const uint32_t* d_cigar_or_len, const u
     SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL((k_cigar_tiles<SOA, kTileOps, ALO_TABLE>), dim3(blocks_all), dim3(64 * kWaves), 0, ctx->stream, a);
     SVX_TRY(svx_timing_mark(ctx, 2));
-    if (ctx->want_dom) {  // somebody pipelines against this context (svx_ctx_wait_dominant)
-        if (!ctx->ev_dom) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dom, hipEventDisableTiming));
-        SVX_HIP(ctx, hipEventRecord(ctx->ev_dom, ctx->stream));
-        ctx->ev_dom_recorded = true;
-    }
+    SVX_TRY(record_dominant(ctx));
     hipLaunchKernelGGL(k_desc_scan, dim3(n_scan_blocks), dim3(kScanBlock), 0, ctx->stream, a.desc, n_tiles,
                        a.out_base, a.carry_ref, a.carry_read, a.dense_list, a.n_dense, a.blk_agg,
                        a.blk_prefix, a.n_dense + 1, d_n_out);
