@@ -595,7 +595,7 @@ int svx_pair_partition_dev_bits(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n
  * (SVIM_COMBINE.py:50,64,76,88,100).  Sequences are bytes in one pool;
  * pair p compares seq[a_off[p] .. a_off[p]+a_len[p]) with
  * seq[b_off[p] .. b_off[p]+b_len[p)).  dist[p] receives the exact distance when
- * it is <= k_max and any value > k_max otherwise (complete linkage cut at
+ * it is <= k_max and 0xFFFFFFFF otherwise (complete linkage cut at
  * max_edit_distance only needs "> t").  k_max = 0xFFFFFFFF
  * requests exact distances.
  */

@@ -81,11 +81,16 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// symbol of a byte value: 0 .. CAP - 1, or CAP for a byte the pattern lacks — which a byte cannot hold at CAP = 256
+template <int CAP>
+using ed_code_t = std::conditional_t<(CAP > 255), uint16_t, uint8_t>;
+
 template <int CAP>
 __global__ __launch_bounds__(64) void k_edit_myers(EdArgs p) {
+    using code_t = ed_code_t<CAP>;
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     uint64_t* peq = lds;                                                  // [(CAP + 1) * 64]
-    uint8_t* cmap = reinterpret_cast<uint8_t*>(peq + (CAP + 1) * 64);     // byte value -> symbol (CAP: absent)
+    code_t* cmap = reinterpret_cast<code_t*>(peq + (CAP + 1) * 64);       // byte value -> symbol (CAP: absent)
     uint32_t* present = reinterpret_cast<uint32_t*>(cmap + 256);          // 256-bit set of pattern bytes
     const uint32_t lane = threadIdx.x;
     const uint32_t w = blockIdx.x;
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(64) void k_edit_myers(EdArgs p) {
             uint32_t rank = __popc(word & ((1u << bit) - 1u));
 #pragma unroll
             for (int j = 0; j < 8; ++j) rank += ((uint32_t)j == (v >> 5)) ? below[j] : 0u;
-            cmap[v] = ((word >> bit) & 1u) ? (uint8_t)rank : (uint8_t)CAP;
+            cmap[v] = ((word >> bit) & 1u) ? (code_t)rank : (code_t)CAP;
         }
     }
     wave_lds_fence();
@@ -423,7 +428,7 @@ __global__ __launch_bounds__(64) void k_edit_myers(EdArgs p) {
 }
 
 template <int CAP>
-constexpr size_t lds_bytes() { return (size_t)(CAP + 1) * 64 * 8 + 256 + 32; }
+constexpr size_t lds_bytes() { return (size_t)(CAP + 1) * 64 * 8 + 256 * sizeof(ed_code_t<CAP>) + 32; }
 
 // ---- wavefront (diagonal-transition) pass in front of the bit-vector kernel -------------------------
 // The haplotypes the PAIR step compares are long and nearly identical (two alleles of one variant plus
