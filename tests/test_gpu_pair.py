@@ -1,6 +1,10 @@
 """HIP stable radix sort + partition (svx_pair_partition) vs the CPU oracle.
 
 Reference: form_partitions (SVIM_COMBINE.py:15-32).
+
+Random keys: which window, run count, digit plan or sweep span an input meets is left to chance here.  The plans' corners
+(5120 | 5121 keys in a window, 32 | 33 runs, two chunks per sweep workgroup, ...) are pinned by the case table of
+tests/pair_cases.py, run on the device by tests/test_gpu_pair_cases.py (Yardstick).
 """
 import numpy as np
 import pytest
