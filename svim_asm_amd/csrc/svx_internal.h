@@ -79,6 +79,10 @@ int svx_ws_reserve(svx_ctx* ctx, size_t total);
 // with the stream synchronised: SVX_OK, or SVX_E_HIP after clearing the header for the calls to come.
 #define SVX_WS_BARRIER_NOTE_WORD 80
 int svx_barrier_check(svx_ctx* ctx);
+// The arrival counters of the pair sort in the same header: the partition sweep's pair (arrivals, leavers:
+// zero between calls) and the first of k_pair_single's two sets of two, which alternate launches use in turn
+#define SVX_WS_SWEEP_COUNTERS_WORD 64
+#define SVX_WS_SINGLE_COUNTERS_WORD 68
 int svx_stage_reserve(svx_ctx* ctx, size_t total);
 // workspace bytes svx_cigar_extract*_dev / svx_segments_postpass_dev reserve for a batch (svx_collect_batch_dev sums them)
 size_t svx_cigar_extract_ws_need(const svx_ctx* ctx, uint64_t n_ops);

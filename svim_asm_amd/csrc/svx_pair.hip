@@ -31,6 +31,9 @@
 //   k_partition      boundary flags straight from the sorted dense keys (they expand back to the original
 //                    keys: no gather) + inclusive scan → partition ids, perm, n_parts.  At most half a
 //                    workgroup per CU with one arrival counter (every workgroup of the grid is resident).
+// Written once for all plans: opens (the border rule), stable_place (the ranking step of a counting pass), sweep_bits /
+// sweep_ids (a thread's run of consecutive sorted keys: flags, then ids), block_scan_1024 over svx_scan_dev.h's wave_scan,
+// and the two barriers (grid_barrier, arrive_wait_leave).
 // Integer work, 20 B per candidate algorithmic, no MFMA; at the product's 60 k candidates it is bound by
 // dependent latencies (launches, grid barriers, LDS passes), not by bytes.  Determinism: ranks
 // come from prefix sums only; the histogram atomics are commutative counts.
@@ -39,7 +42,6 @@
 
 namespace {
 
-constexpr int kBarrierNoteWord = SVX_WS_BARRIER_NOTE_WORD;
 constexpr int kMaxDigitBits = 9;
 constexpr int kBuckets = 1 << kMaxDigitBits;
 constexpr uint32_t kSingleBlockMax = 16384;  // one workgroup sweeps up to two chunks itself
@@ -51,6 +53,13 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// what another workgroup reads inside a launch: agent-scope atomic stores and loads on both sides, no cache-wide
+// release / acquire fences needed
+template <typename T>
+__device__ __forceinline__ void agent_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ T agent_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // Waiting for the other workgroups of a launch is bounded: after kBarrierTicks of the 100 MHz clock (20 s —
 // every workgroup of these grids is resident unless more than four contexts run them on one device) the
 // workgroup notes it in the workspace header and leaves the kernel (what the others would have published is
@@ -61,14 +70,47 @@ __device__ __forceinline__ void wave_lds_sync() {
 #endif
 __device__ __forceinline__ bool spin_until(const uint32_t* c, uint32_t want, uint32_t* timed_out) {
     const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+    while (agent_load(c) < want) {
         __builtin_amdgcn_s_sleep(1);
         if (wall_clock64() - t0 > SVX_EXP_BARRIER_TICKS) {
-            __hip_atomic_store(timed_out, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            agent_store(timed_out, 1u);
             return false;
         }
     }
     return true;
+}
+
+// k_pair_single's barrier.  All threads: the workgroup's earlier agent-scope stores are out, then one thread meets
+// the other workgroups at counter c.  Nobody counts the leavers: the counters come in two sets used by alternate
+// launches of a context, and the last workgroup to arrive at the FIRST barrier of a launch puts the set of
+// the launch before (long finished: same stream) back to zero — one round trip less per barrier.
+__device__ __forceinline__ bool grid_barrier(uint32_t* c, uint32_t* stale, uint32_t* note) {
+    __shared__ uint32_t s_met;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t before = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (stale && before == gridDim.x - 1) {
+            agent_store(stale, 0u);
+            agent_store(stale + 1, 0u);
+        }
+        s_met = (before == gridDim.x - 1 || spin_until(c, gridDim.x, note)) ? 1u : 0u;
+    }
+    __syncthreads();
+    return s_met != 0;  // false: the wait ran out, the caller leaves the kernel
+}
+
+// k_partition<0>'s barrier, one thread of the workgroup after its agent-scope stores: arrive at c[0], wait for the grid,
+// count the leavers in c[1]; the last workgroup to leave puts both back to zero for the next call.  (After a wait
+// that ran out the caller's carry-in is wrong; every store of its stays inside the outputs.)
+__device__ __forceinline__ void arrive_wait_leave(uint32_t* c, uint32_t* note) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)spin_until(c, gridDim.x, note);
+    if (__hip_atomic_fetch_add(c + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+        agent_store(c, 0u);
+        agent_store(c + 1, 0u);
+    }
 }
 
 struct KeyFields {  // dense = OR over f of ((key >> shift[f]) & mask[f]) << off[f]
@@ -94,6 +136,97 @@ __device__ __forceinline__ uint64_t dense_key(const KeyFields& f, uint64_t k) {
     for (uint32_t i = 0; i < 4; ++i)
         if (i < f.n) d |= ((k >> f.shift[i]) & f.mask[i]) << f.off[i];
     return d;
+}
+
+// every set bit of an original key lies inside the fields (the caller's key_bits cover all keys), so the
+// dense key expands back to it exactly: the sweep reads the sorted keys contiguously, no gather
+__device__ __forceinline__ uint64_t original_key(const KeyFields& f, uint64_t d) {
+    uint64_t k = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+        if (i < f.n) k |= ((d >> f.off[i]) & f.mask[i]) << f.shift[i];
+    return k;
+}
+
+// THE border rule (SVIM_COMBINE.py:24-26), on two original keys that are neighbours in sorted order: `cur` opens a
+// partition when type / contig differ or the positions lie more than max_dist apart.  Every flag of every plan is this.
+__device__ __forceinline__ bool opens(uint64_t prev, uint64_t cur, uint32_t max_dist) {
+    const uint32_t pa = (uint32_t)prev, pc = (uint32_t)cur;
+    const uint32_t dist = pa > pc ? pa - pc : pc - pa;
+    return (prev >> 32) != (cur >> 32) || dist > max_dist;
+}
+__device__ __forceinline__ bool opens_partition(const KeyFields& f, uint64_t prev_dense, uint64_t cur_dense, uint32_t max_dist) {
+    return opens(original_key(f, prev_dense), original_key(f, cur_dense), max_dist);
+}
+
+// The stable ranking step of a counting pass, one wave and 64 consecutive keys (the valid lanes are a prefix of the
+// wave, at least one): the lanes with my digit (`bits` wide) by match masks, my rank among them, my place behind the
+// digit's running position run[dig], which the first lane of every digit then advances by the digit's lanes.  The two
+// wave syncs order the LDS accesses of the lanes of this wave, the only one that touches `run`: every read of run[dig]
+// before the advance, the advance before the next step's reads.
+__device__ __forceinline__ uint32_t stable_place(uint32_t* run, uint32_t dig, bool valid, uint32_t bits, int lane) {
+    uint64_t m = __ballot(valid);
+    for (uint32_t bit = 0; bit < bits; ++bit) {
+        const uint64_t bal = __ballot((dig >> bit) & 1u);
+        m &= ((dig >> bit) & 1u) ? bal : ~bal;
+    }
+    const uint32_t rank = __popcll(m & ((1ull << lane) - 1ull));
+    uint32_t pos = 0;
+    if (valid) pos = run[dig] + rank;
+    wave_lds_sync();
+    if (valid && rank == 0) run[dig] += __popcll(m);
+    wave_lds_sync();
+    return pos;
+}
+
+// inclusive scan of `v` over a 1024-thread workgroup; returns the scanned value, *total the sum.
+// TAIL_SYNC = false: the caller has a barrier of its own before s_w is written again.
+template <bool TAIL_SYNC = true>
+__device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* s_w, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t s = wave_scan(v, OpAdd32());
+    if (lane == 63) s_w[wave] = s;
+    __syncthreads();
+    uint32_t wp = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+        const uint32_t x = s_w[w];
+        if (w < wave) wp += x;
+        tot += x;
+    }
+    if (TAIL_SYNC) __syncthreads();
+    *total = tot;
+    return wp + s;
+}
+
+// The per-thread sweep over sorted keys: a thread looks at the up to `per` <= MAX consecutive positions from j0 inside
+// [.., end), remembers the key before each (the one before position 0 reads as 0) and sets bit i where
+// pred(key before, key, position) holds at position j0 + i.  key(j) is read once per position.
+template <int MAX, typename Key, typename Pred>
+__device__ __forceinline__ uint32_t sweep_bits(uint32_t j0, uint32_t end, uint32_t per, Key key, Pred pred) {
+    uint32_t bits = 0;
+    if (j0 >= end) return 0;
+    uint64_t prev = j0 ? key(j0 - 1) : 0ull;
+#pragma unroll
+    for (uint32_t i = 0; i < MAX; ++i) {
+        const uint32_t j = j0 + i;
+        if (i < per && j < end) {
+            const uint64_t c = key(j);
+            if (pred(prev, c, j)) bits |= 1u << i;
+            prev = c;
+        }
+    }
+    return bits;
+}
+// ... and its other half: `id` counts the bits set before this thread's positions (from a scan of the popcounts),
+// position j0 + i gets store(j0 + i, id + the thread's bits up to i)
+template <int MAX, typename Store>
+__device__ __forceinline__ void sweep_ids(uint32_t bits, uint32_t id, uint32_t j0, uint32_t end, uint32_t per, Store store) {
+#pragma unroll
+    for (uint32_t i = 0; i < MAX; ++i) {
+        const uint32_t j = j0 + i;
+        if (i < per && j < end) store(j, id += (bits >> i) & 1u);
+    }
 }
 
 __global__ __launch_bounds__(256) void k_key_or(const uint64_t* __restrict__ keys, uint32_t n,
@@ -189,12 +322,7 @@ __global__ __launch_bounds__(256) void k_radix_pass(PairBufs b, uint32_t pass) {
         if (base + it * 64 + lane < b.n) atomicAdd(&s_run[wave][(uint32_t)(key[it] >> shift) & dmask], 1u);
     // exclusive scan of the bucket totals over the workgroup (thread t holds buckets 2t, 2t+1)
     {
-        uint32_t s = total0 + total1;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t t = __shfl_up(s, k);
-            if (lane >= k) s += t;
-        }
+        const uint32_t s = wave_scan(total0 + total1, OpAdd32());
         if (lane == 63) s_w[wave] = s;
         __syncthreads();  // also: every wave's counts are in s_run
         uint32_t wp = 0;
@@ -214,106 +342,61 @@ __global__ __launch_bounds__(256) void k_radix_pass(PairBufs b, uint32_t pass) {
     __syncthreads();
 
     // ---- one wave per quarter block: stable ranking with match masks, scatter, next digit's counts
-    uint32_t* run = s_run[wave];
-    const uint64_t lt = (1ull << lane) - 1ull;
     const uint32_t nshift = shift + b.digit_bits;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
-        const uint32_t i = base + it * 64 + lane;
-        const bool valid = i < b.n;
-        const uint32_t dig = (uint32_t)(key[it] >> shift) & dmask;
-        uint64_t m = __ballot(valid);
-        if (m == 0) break;  // wave-uniform: nothing left in this quarter
-        for (uint32_t bit = 0; bit < b.digit_bits; ++bit) {
-            const uint64_t bal = __ballot((dig >> bit) & 1u);
-            m &= ((dig >> bit) & 1u) ? bal : ~bal;
-        }
-        const uint32_t rank = __popcll(m & lt);
-        uint32_t pos = 0;
-        if (valid) pos = run[dig] + rank;
-        wave_lds_sync();
-        if (valid && rank == 0) run[dig] += __popcll(m);
-        wave_lds_sync();
+        const bool valid = base + it * 64 + lane < b.n;
+        if (__ballot(valid) == 0) break;  // wave-uniform: nothing left in this quarter
+        const uint32_t pos = stable_place(s_run[wave], (uint32_t)(key[it] >> shift) & dmask, valid, b.digit_bits, lane);
         if (valid) {
-#ifndef SVX_EXP_NOSCATTER  // (ablation builds only)
             dk[pos] = key[it];
             di[pos] = id[it];
-#endif
-#ifndef SVX_EXP_NOHNEXT  // (ablation builds only)
             if (hnext) atomicAdd(&hnext[(size_t)(pos / kBlockKeys) * kBuckets + ((uint32_t)(key[it] >> nshift) & dmask)], 1u);
-#endif
         }
     }
 }
+
+struct PairCall {  // what every plan's last kernel has of the call
+    KeyFields f;   // dense <-> original key
+    uint32_t n, max_dist;
+    uint32_t *perm, *part_id, *n_parts;
+    uint32_t* note;  // workspace header: set when a wait ran out (svx_barrier_check)
+};
 
 struct PartArgs {
     const uint64_t* sorted_keys;  // dense keys in sorted order (after the last pass)
     const uint32_t* sorted;       // the permutation that goes with them
-    KeyFields f;                  // dense -> original key
-    uint32_t n;
-    uint32_t max_dist;
-    uint32_t* perm;
-    uint32_t* part_id;
-    uint32_t* n_parts;
+    PairCall c;
     uint32_t* block_tot;      // [gridDim.x] flags per workgroup (multi-block form)
-    uint32_t* counter;        // self-cleaning arrival counter (workspace header)
+    uint32_t* counter;        // workspace header: arrivals and leavers of k_partition<0>, zero between calls
 };
-
-// every set bit of an original key lies inside the fields (the caller's key_bits cover all keys), so the
-// dense key expands back to it exactly: the sweep reads the sorted keys contiguously, no gather
-__device__ __forceinline__ uint64_t original_key(const KeyFields& f, uint64_t d) {
-    uint64_t k = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i)
-        if (i < f.n) k |= ((d >> f.off[i]) & f.mask[i]) << f.shift[i];
-    return k;
-}
-
-// inclusive sum over the wave: the DPP ladder of svx_scan_dev.h
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) { return wave_scan(v, OpAdd32()); }
-
-// inclusive scan of `v` over a 1024-thread workgroup; returns the scanned value, *total the sum.
-// TAIL_SYNC = false: the caller has a barrier of its own before s_w is written again.
-template <bool TAIL_SYNC = true>
-__device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* s_w, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t s = wave_scan_incl(v);
-    if (lane == 63) s_w[wave] = s;
-    __syncthreads();
-    uint32_t wp = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const uint32_t x = s_w[w];
-        if (w < wave) wp += x;
-        tot += x;
-    }
-    if (TAIL_SYNC) __syncthreads();
-    *total = tot;
-    return wp + s;
-}
 
 constexpr int kPartPer = 8;                       // consecutive sorted keys per thread and chunk
 constexpr uint32_t kPartChunk = 1024u * kPartPer; // keys one workgroup sweeps per scan
 
-// Boundary flags of the thread's kPartPer consecutive positions of chunk [base, base + kPartChunk) ∩ [.., hi):
-// bit i of the result = position base + tid * kPartPer + i opens a partition (SVIM_COMBINE.py:24-26).
+// Boundary flags of the thread's `per` consecutive positions from j0 of the sorted dense keys sk[0 .. end): bit i of
+// the result = position j0 + i opens a partition (position 0 never does)
+template <int MAX>
+__device__ __forceinline__ uint32_t border_bits(const PairCall& c, const uint64_t* sk, uint32_t j0, uint32_t end,
+                                                uint32_t per) {
+    return sweep_bits<MAX>(j0, end, per, [&](uint32_t j) { return original_key(c.f, sk[j]); },
+                           [&](uint64_t prev, uint64_t cur, uint32_t j) { return j && opens(prev, cur, c.max_dist); });
+}
+// ... of chunk [base, base + kPartChunk) ∩ [.., hi) of the sweep, kPartPer positions per thread
 __device__ __forceinline__ uint32_t chunk_flags(const PartArgs& p, uint32_t base, uint32_t hi) {
-    const uint32_t j0 = base + threadIdx.x * kPartPer;
-    if (j0 >= hi) return 0;
-    uint64_t prev = j0 ? original_key(p.f, p.sorted_keys[j0 - 1]) : 0;
-    uint32_t bits = 0;
-#pragma unroll
-    for (int i = 0; i < kPartPer; ++i) {
-        const uint32_t j = j0 + i;
-        if (j < hi) {
-            const uint64_t c = original_key(p.f, p.sorted_keys[j]);
-            const uint32_t pa = (uint32_t)prev, pc = (uint32_t)c;
-            const uint32_t dist = pa > pc ? pa - pc : pc - pa;
-            if (j && ((prev >> 32) != (c >> 32) || dist > p.max_dist)) bits |= 1u << i;
-            prev = c;
-        }
+    return border_bits<kPartPer>(p.c, p.sorted_keys, base + threadIdx.x * kPartPer, hi, kPartPer);
+}
+
+// the flags of the range [lo, hi), counted chunk by chunk and summed over the workgroup; *kept: the thread's flags of
+// the range's last chunk
+__device__ __forceinline__ uint32_t range_flags(const PartArgs& p, uint32_t lo, uint32_t hi, uint32_t* s_w, uint32_t* kept) {
+    uint32_t cnt = 0, tot;
+    for (uint32_t base = lo; base < hi; base += kPartChunk) {
+        *kept = chunk_flags(p, base, hi);
+        cnt += __popc(*kept);
     }
-    return bits;
+    (void)block_scan_1024(cnt, s_w, &tot);
+    return tot;
 }
 
 // Workgroup g owns the contiguous range [g * span, (g + 1) * span) of the sorted keys, swept in chunks of
@@ -327,14 +410,11 @@ __device__ __forceinline__ uint32_t chunk_flags(const PartArgs& p, uint32_t base
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_partition(PartArgs p, uint32_t span) {
     __shared__ uint32_t s_w[16];
-    const uint32_t lo = blockIdx.x * span, hi = min(p.n, lo + span);
+    const uint32_t lo = blockIdx.x * span, hi = min(p.c.n, lo + span);
     const bool one_chunk = MODE == 0 && hi - lo <= kPartChunk;
     uint32_t carry = 0, kept = 0;
     if (MODE == 1) {
-        uint32_t cnt = 0;
-        for (uint32_t base = lo; base < hi; base += kPartChunk) cnt += __popc(chunk_flags(p, base, hi));
-        uint32_t tot;
-        (void)block_scan_1024(cnt, s_w, &tot);
+        const uint32_t tot = range_flags(p, lo, hi, s_w, &kept);
         if (threadIdx.x == 0) p.block_tot[blockIdx.x] = tot;
         return;
     }
@@ -343,50 +423,27 @@ __global__ __launch_bounds__(1024) void k_partition(PartArgs p, uint32_t span) {
         (void)block_scan_1024(v, s_w, &carry);
     }
     if (MODE == 0 && gridDim.x > 1) {
-        uint32_t cnt = 0;
-        for (uint32_t base = lo; base < hi; base += kPartChunk) {
-            kept = chunk_flags(p, base, hi);
-            cnt += __popc(kept);
-        }
-        uint32_t tot;
-        (void)block_scan_1024(cnt, s_w, &tot);
+        const uint32_t tot = range_flags(p, lo, hi, s_w, &kept);
         if (threadIdx.x == 0) {
-            // block_tot is the only data another workgroup reads inside this launch: agent-scope atomic
-            // store and loads on both sides, no cache-wide release / acquire fences needed
-            __hip_atomic_store(&p.block_tot[blockIdx.x], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(p.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // (after a wait that ran out the carry-in is wrong, every store stays inside the outputs)
-            (void)spin_until(p.counter, gridDim.x, p.counter + (kBarrierNoteWord - 64));
-            // the last workgroup to get here puts the counter back to zero for the next call
-            if (__hip_atomic_fetch_add(p.counter + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-                __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(p.counter + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            agent_store(&p.block_tot[blockIdx.x], tot);  // the only data another workgroup reads inside this launch
+            arrive_wait_leave(p.counter, p.c.note);
         }
         __syncthreads();
         // exclusive sum of the earlier workgroups' flags: one load per thread (fewer than 1024 workgroups)
-        const uint32_t v = threadIdx.x < blockIdx.x
-                               ? __hip_atomic_load(&p.block_tot[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const uint32_t v = threadIdx.x < blockIdx.x ? agent_load(&p.block_tot[threadIdx.x]) : 0u;
         (void)block_scan_1024(v, s_w, &carry);
     }
     for (uint32_t base = lo; base < hi; base += kPartChunk) {
         const uint32_t bits = (one_chunk && gridDim.x > 1) ? kept : chunk_flags(p, base, hi);
         uint32_t tot;
-        uint32_t id = carry + block_scan_1024(__popc(bits), s_w, &tot) - __popc(bits);  // partitions opened before this thread
-        const uint32_t j0 = base + threadIdx.x * kPartPer;
-#pragma unroll
-        for (int i = 0; i < kPartPer; ++i) {
-            const uint32_t j = j0 + i;
-            if (j < hi) {
-                id += (bits >> i) & 1u;
-                p.part_id[j] = id;
-                p.perm[j] = p.sorted[j];
-            }
-        }
+        const uint32_t before = carry + block_scan_1024(__popc(bits), s_w, &tot) - __popc(bits);  // opened before this thread
+        sweep_ids<kPartPer>(bits, before, base + threadIdx.x * kPartPer, hi, kPartPer, [&](uint32_t j, uint32_t id) {
+            p.c.part_id[j] = id;
+            p.c.perm[j] = p.sorted[j];
+        });
         carry += tot;
     }
-    if (threadIdx.x == 0 && hi == p.n) *p.n_parts = p.n ? carry + 1 : 0;
+    if (threadIdx.x == 0 && hi == p.c.n) *p.c.n_parts = p.c.n ? carry + 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -428,14 +485,10 @@ struct SingleArgs {
     uint32_t* gidx;       // [2][n]
     uint32_t* win;        // [grid][2]: flags inside the window, keys in the window
     uint64_t* win_keys;   // [grid][2]: first and last key of the sorted window
-    KeyFields f;
-    uint32_t n, live, max_dist, target, slice_len;
-    uint32_t* perm;
-    uint32_t* part_id;
-    uint32_t* n_parts;
+    PairCall c;
+    uint32_t live, target, slice_len;
     uint32_t* counter;        // workspace header: this launch's two arrival counters
     uint32_t* counter_stale;  // the two of the launch before
-    uint32_t* note;           // set when a wait ran out (svx_barrier_check)
 };
 
 #ifdef SVX_EXP_PAIRCLK  // (timeline builds only: 100 MHz clock stamps of thread 0 of every workgroup)
@@ -447,31 +500,6 @@ __device__ unsigned long long g_pair_clk[64 * 16];
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <typename T>
-__device__ __forceinline__ void agent_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ T agent_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// all threads: the workgroup's earlier agent-scope stores are out, then one thread meets the other
-// workgroups at counter c.  Nobody counts the leavers: the counters come in two sets used by alternate
-// launches of a context, and the last workgroup to arrive at the FIRST barrier of a launch puts the set of
-// the launch before (long finished: same stream) back to zero — one round trip less per barrier.
-__device__ __forceinline__ bool grid_barrier(uint32_t* c, uint32_t* stale, uint32_t* note) {
-    __shared__ uint32_t s_met;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t before = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (stale && before == gridDim.x - 1) {
-            agent_store(stale, 0u);
-            agent_store(stale + 1, 0u);
-        }
-        s_met = (before == gridDim.x - 1 || spin_until(c, gridDim.x, note)) ? 1u : 0u;
-    }
-    __syncthreads();
-    return s_met != 0;  // false: the wait ran out, the caller leaves the kernel
-}
-
 // hist[dig] += length of every run of equal digits among the wave's valid lanes (the valid lanes are a
 // prefix of the wave): one LDS atomic per run instead of one per key — keys arrive nearly sorted
 __device__ __forceinline__ void count_runs(uint32_t* hist, uint32_t dig, bool valid, int lane) {
@@ -482,13 +510,6 @@ __device__ __forceinline__ void count_runs(uint32_t* hist, uint32_t dig, bool va
         const uint64_t nxt = (heads >> lane) >> 1;
         atomicAdd(&hist[dig], nxt ? (uint32_t)__ffsll((unsigned long long)nxt) : 64u - (uint32_t)lane);
     }
-}
-
-__device__ __forceinline__ bool opens_partition(const KeyFields& f, uint64_t prev_dense, uint64_t cur_dense, uint32_t max_dist) {
-    const uint64_t a = original_key(f, prev_dense), c = original_key(f, cur_dense);
-    const uint32_t pa = (uint32_t)a, pc = (uint32_t)c;
-    const uint32_t dist = pa > pc ? pa - pc : pc - pa;
-    return (a >> 32) != (c >> 32) || dist > max_dist;
 }
 
 // One stable counting pass over the window: digit(key) = ((key >> shift) & mask) - sub, `bits` wide.
@@ -520,256 +541,232 @@ __device__ __forceinline__ void window_pass(const uint64_t* sk, const uint32_t* 
         for (int w = 0; w < 16; ++w) { s_cnt[w * kFine + tid] = base; base += c[w]; }
     }
     __syncthreads();
-    uint32_t* run = s_cnt + wave * kFine;
-    const uint64_t lt = (1ull << lane) - 1ull;
     for (uint32_t it = 0; it < per; ++it) {
         const uint32_t j = wbase + it * 64 + lane;
         const bool valid = j < M;
-        uint64_t m = __ballot(valid);
-        if (m == 0) break;
+        if (__ballot(valid) == 0) break;
         uint64_t key = 0;
         uint32_t id = 0;
         if (valid) { key = sk[j]; id = si[j]; }
-        const uint32_t dig = ((uint32_t)(key >> shift) & mask) - sub;
-        for (uint32_t bit = 0; bit < bits; ++bit) {
-            const uint64_t bal = __ballot((dig >> bit) & 1u);
-            m &= ((dig >> bit) & 1u) ? bal : ~bal;
-        }
-        const uint32_t rank = __popcll(m & lt);
-        uint32_t pos = 0;
-        if (valid) pos = run[dig] + rank;
-        wave_lds_sync();
-        if (valid && rank == 0) run[dig] += __popcll(m);
-        wave_lds_sync();
+        const uint32_t pos = stable_place(s_cnt + wave * kFine, ((uint32_t)(key >> shift) & mask) - sub, valid, bits, lane);
         if (valid) { dk[pos] = key; di[pos] = id; }
     }
     __syncthreads();
 }
 
-template <bool LDS>
-__device__ __forceinline__ void window_work(const SingleArgs& a, char* s_dyn, uint32_t* s_cnt, uint32_t* s_w,
-                                            const uint32_t* s_soff, const uint32_t* s_scnt, uint32_t lo, uint32_t hi,
-                                            uint32_t start, uint32_t M, uint32_t low_bits) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // both halves of a ping-pong pair hang off one base pointer (LDS or HBM scratch): half h is base + h * stride
-    uint64_t* kbase;
-    uint32_t* ibase;
-    uint32_t stride;
-    if constexpr (LDS) {
-        kbase = reinterpret_cast<uint64_t*>(s_dyn);
-        ibase = reinterpret_cast<uint32_t*>(s_dyn + 2 * kWinCap * 8);
-        stride = kWinCap;
-    } else {
-        kbase = a.gkey + start;
-        ibase = a.gidx + start;
-        stride = a.n;
-    }
-    auto K = [&](int h) { return kbase + (size_t)h * stride; };
-    auto I = [&](int h) { return ibase + (size_t)h * stride; };
-    // ---- gather, input order: slice s puts its share at s_soff[s].  One 16-byte sc1 load per lane and group
-    // of 128 keys (keys 2 * lane and 2 * lane + 1 of the group), a batch of groups in flight before the first
-    // is looked at; a slice is left as soon as its share has been found
+// ---- the steps of a window, in the order of the comment above; K(h) / I(h) are the window's two key and index buffers
+
+// gather, input order: slice s puts its share at s_soff[s].  One 16-byte sc1 load per lane and group of 128 keys (keys
+// 2 * lane and 2 * lane + 1 of the group), a batch of groups in flight before the first is looked at; a slice is left
+// as soon as its share has been found
+__device__ __forceinline__ void window_gather(const SingleArgs& a, const uint32_t* s_soff, const uint32_t* s_scnt, uint32_t lo,
+                                              uint32_t hi, uint32_t low_bits, uint64_t* dk, uint32_t* di) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t lt = (1ull << lane) - 1ull;
-    {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.dense, 0, (int)(a.n * 8u), 0x00020000);
-        for (uint32_t s = wave; s < gridDim.x; s += 16) {
-            const uint32_t share = s_scnt[s];
-            if (!share) continue;
-            uint32_t run = s_soff[s];
-            const uint32_t end = run + share;
-            const uint32_t sl = s * a.slice_len, sh = min(a.n, sl + a.slice_len);
-            for (uint32_t base = sl; base < sh && run < end; base += 128 * kGatherBatch) {
-                u32x4 d[kGatherBatch];
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.dense, 0, (int)(a.c.n * 8u), 0x00020000);
+    for (uint32_t s = wave; s < gridDim.x; s += 16) {
+        const uint32_t share = s_scnt[s];
+        if (!share) continue;
+        uint32_t run = s_soff[s];
+        const uint32_t end = run + share;
+        const uint32_t sl = s * a.slice_len, sh = min(a.c.n, sl + a.slice_len);
+        for (uint32_t base = sl; base < sh && run < end; base += 128 * kGatherBatch) {
+            u32x4 d[kGatherBatch];
 #pragma unroll
-                for (int u = 0; u < kGatherBatch; ++u) {
-                    const uint32_t i0 = base + u * 128 + 2 * lane;
-                    d[u] = u32x4{0u, 0u, 0u, 0u};
-                    if (i0 < sh) d[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, i0 * 8u, 0, 16);
-                }
+            for (int u = 0; u < kGatherBatch; ++u) {
+                const uint32_t i0 = base + u * 128 + 2 * lane;
+                d[u] = u32x4{0u, 0u, 0u, 0u};
+                if (i0 < sh) d[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, i0 * 8u, 0, 16);
+            }
 #pragma unroll
-                for (int u = 0; u < kGatherBatch; ++u) {
-                    const uint32_t i0 = base + u * 128 + 2 * lane;
-                    const uint64_t k0 = ((uint64_t)d[u].y << 32) | d[u].x, k1 = ((uint64_t)d[u].w << 32) | d[u].z;
-                    const uint32_t f0 = (uint32_t)(k0 >> low_bits), f1 = (uint32_t)(k1 >> low_bits);
-                    const bool in0 = i0 < sh && f0 >= lo && f0 < hi, in1 = i0 + 1 < sh && f1 >= lo && f1 < hi;
-                    const uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
-                    const uint32_t below = run + __popcll(b0 & lt) + __popcll(b1 & lt);
-                    if (in0) { K(0)[below] = k0; I(0)[below] = i0; }
-                    if (in1) { K(0)[below + (in0 ? 1u : 0u)] = k1; I(0)[below + (in0 ? 1u : 0u)] = i0 + 1; }
-                    run += __popcll(b0) + __popcll(b1);
-                }
+            for (int u = 0; u < kGatherBatch; ++u) {
+                const uint32_t i0 = base + u * 128 + 2 * lane;
+                const uint64_t k0 = ((uint64_t)d[u].y << 32) | d[u].x, k1 = ((uint64_t)d[u].w << 32) | d[u].z;
+                const uint32_t f0 = (uint32_t)(k0 >> low_bits), f1 = (uint32_t)(k1 >> low_bits);
+                const bool in0 = i0 < sh && f0 >= lo && f0 < hi, in1 = i0 + 1 < sh && f1 >= lo && f1 < hi;
+                const uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
+                const uint32_t below = run + __popcll(b0 & lt) + __popcll(b1 & lt);
+                if (in0) { dk[below] = k0; di[below] = i0; }
+                if (in1) { dk[below + (in0 ? 1u : 0u)] = k1; di[below + (in0 ? 1u : 0u)] = i0 + 1; }
+                run += __popcll(b0) + __popcll(b1);
             }
         }
     }
     __syncthreads();
-    PAIR_CLK(5);
-    // ---- the window as it was gathered is a few sorted runs when the caller's lists were ordered (PAIR
-    // hands over the haplotype-1 list, then the haplotype-2 list, each along the genome: two runs, a few more
-    // where alignments overlap): up to kMergeRuns runs are merged pairwise, one binary search per key and
-    // round; equal keys: the earlier run first, so input order is kept.  More runs: counting passes.
-    int src = 0;
-    bool sorted = false;
-    if constexpr (LDS) {
-        __shared__ uint32_t s_run[kMergeRuns + 2];
-        const uint32_t per = (M + 1023) >> 10, j0 = tid * per;
-        uint32_t bits = 0;
-        if (j0 < M) {
-            uint64_t prev = j0 ? K(0)[j0 - 1] : 0ull;
+}
+
+// merge of runs (LDS windows): the window as it was gathered is a few sorted runs when the caller's lists were ordered
+// (PAIR hands over the haplotype-1 list, then the haplotype-2 list, each along the genome: two runs, a few more where
+// alignments overlap): up to kMergeRuns runs are merged pairwise, one binary search per key and round; equal keys: the
+// earlier run first, so input order is kept.  Returns false, nothing moved, for more runs: counting passes.
+template <typename KF, typename IF>
+__device__ __forceinline__ bool window_merge_runs(KF K, IF I, uint32_t M, uint32_t* s_w, int* src) {
+    __shared__ uint32_t s_run[kMergeRuns + 2];
+    const int tid = threadIdx.x;
+    const uint32_t per = (M + 1023) >> 10, j0 = tid * per;
+    const uint32_t bits = sweep_bits<kWinCap / 1024>(j0, M, per, [&](uint32_t j) { return K(0)[j]; },  // the descents
+                                                     [](uint64_t prev, uint64_t c, uint32_t) { return c < prev; });
+    uint32_t descents;
+    uint32_t r = block_scan_1024(__popc(bits), s_w, &descents) - __popc(bits);  // descents before this thread
+    uint32_t runs = descents + 1;
+    if (runs > kMergeRuns) return false;
+    if (tid == 0) { s_run[0] = 0; s_run[runs] = M; }
 #pragma unroll
-            for (uint32_t i = 0; i < kWinCap / 1024; ++i) {
-                const uint32_t j = j0 + i;
-                if (i < per && j < M) {
-                    const uint64_t c = K(0)[j];
-                    if (c < prev) bits |= 1u << i;  // (never at j = 0: prev = 0)
-                    prev = c;
+    for (uint32_t i = 0; i < kWinCap / 1024; ++i)
+        if ((bits >> i) & 1u) s_run[++r] = j0 + i;
+    __syncthreads();
+    while (runs > 1) {
+        const uint64_t* sk = K(*src);
+        const uint32_t* si = I(*src);
+        uint64_t* dk = K(*src ^ 1);
+        uint32_t* di = I(*src ^ 1);
+        for (uint32_t j = tid; j < M; j += 1024) {
+            const uint64_t x = sk[j];
+            uint32_t q = 0;  // the run of position j
+            for (uint32_t t = 1; t < runs; ++t) q += s_run[t] <= j ? 1u : 0u;
+            uint32_t out = j;
+            if ((q & 1u) == 0u && q + 1 < runs) {        // left run of a pair: keys of the right run below x
+                uint32_t lo = s_run[q + 1], hi = s_run[q + 2];
+                const uint32_t first = lo;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (sk[mid] < x) lo = mid + 1; else hi = mid;
                 }
+                out = j + (lo - first);
+            } else if (q & 1u) {                          // right run: keys of the left run up to x
+                uint32_t lo = s_run[q - 1], hi = s_run[q];
+                const uint32_t last = hi;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (sk[mid] <= x) lo = mid + 1; else hi = mid;
+                }
+                out = j - (last - lo);
             }
+            dk[out] = x;
+            di[out] = si[j];
         }
-        uint32_t descents;
-        uint32_t r = block_scan_1024(__popc(bits), s_w, &descents) - __popc(bits);  // descents before this thread
-        uint32_t runs = descents + 1;
-        if (runs <= kMergeRuns) {
-            sorted = true;
-            if (tid == 0) { s_run[0] = 0; s_run[runs] = M; }
-#pragma unroll
-            for (uint32_t i = 0; i < kWinCap / 1024; ++i)
-                if ((bits >> i) & 1u) s_run[++r] = j0 + i;
-            __syncthreads();
-            while (runs > 1) {
-                const uint64_t* sk = K(src);
-                const uint32_t* si = I(src);
-                uint64_t* dk = K(src ^ 1);
-                uint32_t* di = I(src ^ 1);
-                for (uint32_t j = tid; j < M; j += 1024) {
-                    const uint64_t x = sk[j];
-                    uint32_t q = 0;  // the run of position j
-                    for (uint32_t t = 1; t < runs; ++t) q += s_run[t] <= j ? 1u : 0u;
-                    uint32_t out = j;
-                    if ((q & 1u) == 0u && q + 1 < runs) {        // left run of a pair: keys of the right run below x
-                        uint32_t lo = s_run[q + 1], hi = s_run[q + 2];
-                        const uint32_t first = lo;
-                        while (lo < hi) {
-                            const uint32_t mid = (lo + hi) >> 1;
-                            if (sk[mid] < x) lo = mid + 1; else hi = mid;
-                        }
-                        out = j + (lo - first);
-                    } else if (q & 1u) {                          // right run: keys of the left run up to x
-                        uint32_t lo = s_run[q - 1], hi = s_run[q];
-                        const uint32_t last = hi;
-                        while (lo < hi) {
-                            const uint32_t mid = (lo + hi) >> 1;
-                            if (sk[mid] <= x) lo = mid + 1; else hi = mid;
-                        }
-                        out = j - (last - lo);
-                    }
-                    dk[out] = x;
-                    di[out] = si[j];
-                }
-                __syncthreads();
-                const uint32_t merged = (runs + 1) >> 1;
-                if (tid < 64) {  // run q of the next round starts where run 2q started
-                    const uint32_t v = (uint32_t)tid <= merged ? ((uint32_t)tid == merged ? M : s_run[2 * tid]) : 0u;
-                    wave_lds_sync();
-                    if ((uint32_t)tid <= merged) s_run[tid] = v;
-                }
-                __syncthreads();
-                runs = merged;
-                src ^= 1;
-            }
+        __syncthreads();
+        const uint32_t merged = (runs + 1) >> 1;
+        if (tid < 64) {  // run q of the next round starts where run 2q started
+            const uint32_t v = (uint32_t)tid <= merged ? ((uint32_t)tid == merged ? M : s_run[2 * tid]) : 0u;
+            wave_lds_sync();
+            if ((uint32_t)tid <= merged) s_run[tid] = v;
         }
+        __syncthreads();
+        runs = merged;
+        *src ^= 1;
     }
-    // ---- stable LSD passes: the low bits in digits of at most 9, then the bucket number
-    if (!sorted && low_bits) {
+    return true;
+}
+
+// counting passes: stable LSD passes over the low bits in digits of at most 9, then one over the bucket number
+template <typename KF, typename IF>
+__device__ __forceinline__ void window_count_passes(KF K, IF I, uint32_t M, uint32_t* s_cnt, uint32_t* s_w, uint32_t lo,
+                                                    uint32_t hi, uint32_t low_bits, int* src) {
+    if (low_bits) {
         const uint32_t passes = (low_bits + kFineBits - 1) / kFineBits;
         const uint32_t db = (low_bits + passes - 1) / passes;
         for (uint32_t p = 0; p < passes; ++p) {
-            window_pass(K(src), I(src), K(src ^ 1), I(src ^ 1), M, s_cnt, s_w, p * db, (1u << db) - 1u, 0u, db);
-            src ^= 1;
+            window_pass(K(*src), I(*src), K(*src ^ 1), I(*src ^ 1), M, s_cnt, s_w, p * db, (1u << db) - 1u, 0u, db);
+            *src ^= 1;
         }
     }
-    if (!sorted && hi - lo > 1) {
-        window_pass(K(src), I(src), K(src ^ 1), I(src ^ 1), M, s_cnt, s_w, low_bits, kFine - 1u, lo,
+    if (hi - lo > 1) {
+        window_pass(K(*src), I(*src), K(*src ^ 1), I(*src ^ 1), M, s_cnt, s_w, low_bits, kFine - 1u, lo,
                     32u - (uint32_t)__clz((int)(hi - lo - 1)));
-        src ^= 1;
+        *src ^= 1;
     }
-    PAIR_CLK(6);
-    // ---- flags between neighbours, local partition numbers (into the free index buffer)
+}
+
+// local ids: flags between neighbours of the sorted window sk, partition numbers inside the window into ID; returns the
+// window's flag count
+template <bool LDS>
+__device__ __forceinline__ uint32_t window_local_ids(const SingleArgs& a, const uint64_t* sk, uint32_t* ID, uint32_t M,
+                                                     uint32_t* s_w) {
+    const int tid = threadIdx.x;
     uint32_t carry = 0;
-    uint32_t* ID = I(src ^ 1);
     if constexpr (LDS) {  // at most five consecutive keys per thread: one scan for the whole window
         const uint32_t per = (M + 1023) >> 10, j0 = tid * per;
-        uint32_t bits = 0;
-        if (j0 < M) {
-            uint64_t prev = j0 ? original_key(a.f, K(src)[j0 - 1]) : 0ull;
-#pragma unroll
-            for (uint32_t i = 0; i < kWinCap / 1024; ++i) {
-                const uint32_t j = j0 + i;
-                if (i < per && j < M) {
-                    const uint64_t c = original_key(a.f, K(src)[j]);
-                    const uint32_t pa = (uint32_t)prev, pc = (uint32_t)c;
-                    const uint32_t dist = pa > pc ? pa - pc : pc - pa;
-                    if (j && ((prev >> 32) != (c >> 32) || dist > a.max_dist)) bits |= 1u << i;
-                    prev = c;
-                }
-            }
-        }
-        uint32_t id = block_scan_1024<false>(__popc(bits), s_w, &carry) - __popc(bits);
-#pragma unroll
-        for (uint32_t i = 0; i < kWinCap / 1024; ++i) {
-            const uint32_t j = j0 + i;
-            if (i < per && j < M) {
-                id += (bits >> i) & 1u;
-                ID[j] = id;
-            }
-        }
+        const uint32_t bits = border_bits<kWinCap / 1024>(a.c, sk, j0, M, per);
+        const uint32_t before = block_scan_1024<false>(__popc(bits), s_w, &carry) - __popc(bits);
+        sweep_ids<kWinCap / 1024>(bits, before, j0, M, per, [&](uint32_t j, uint32_t id) { ID[j] = id; });
     } else {
         for (uint32_t base = 0; base < M; base += 1024) {
             const uint32_t j = base + tid;
             uint32_t flag = 0;
-            if (j < M && j) flag = opens_partition(a.f, K(src)[j - 1], K(src)[j], a.max_dist) ? 1u : 0u;
+            if (j < M && j) flag = opens_partition(a.c.f, sk[j - 1], sk[j], a.c.max_dist) ? 1u : 0u;
             uint32_t tot;
             const uint32_t incl = block_scan_1024(flag, s_w, &tot);
             if (j < M) ID[j] = carry + incl;
             carry += tot;
         }
     }
-    if (tid == 0) {
-        agent_store(a.win + 2 * blockIdx.x, carry);
-        agent_store(a.win + 2 * blockIdx.x + 1, M);
-        agent_store(a.win_keys + 2 * blockIdx.x, K(src)[0]);
-        agent_store(a.win_keys + 2 * blockIdx.x + 1, K(src)[M - 1]);
-    }
-    PAIR_CLK(7);
-    if (!grid_barrier(a.counter + 1, nullptr, a.note)) return;
-    PAIR_CLK(8);
-    // ---- the table of windows: flag between windows, carry-in
+    return carry;
+}
+
+// the table of windows, behind barrier B: the flag between this window and the filled one before it, and the
+// partitions opened before this window = the carry-in (returned); workgroup 0 writes n_parts
+__device__ __forceinline__ uint32_t window_table(const SingleArgs& a) {
     __shared__ uint32_t s_in[2];
-    if (wave == 0) {
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < 64) {
         const bool have = (uint32_t)lane < gridDim.x;
         const uint32_t cnt = have ? agent_load(a.win + 2 * lane) : 0u;
         const uint32_t m = have ? agent_load(a.win + 2 * lane + 1) : 0u;
         const uint64_t first = (have && m) ? agent_load(a.win_keys + 2 * lane) : 0ull;
         const uint64_t last = (have && m) ? agent_load(a.win_keys + 2 * lane + 1) : 0ull;
-        const uint64_t filled = __ballot(m != 0) & lt;
+        const uint64_t filled = __ballot(m != 0) & ((1ull << lane) - 1ull);
         const int pred = filled ? 63 - __clzll((long long)filled) : 0;
         const uint64_t pl = ((uint64_t)__shfl((uint32_t)(last >> 32), pred) << 32) | __shfl((uint32_t)last, pred);
-        const uint32_t f0 = (m && filled && opens_partition(a.f, pl, first, a.max_dist)) ? 1u : 0u;
-        uint32_t sc = cnt + f0;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t t = __shfl_up(sc, k);
-            if (lane >= k) sc += t;
-        }
+        const uint32_t f0 = (m && filled && opens_partition(a.c.f, pl, first, a.c.max_dist)) ? 1u : 0u;
+        const uint32_t sc = wave_scan(cnt + f0, OpAdd32());
         if ((uint32_t)lane == blockIdx.x) { s_in[0] = sc - cnt; s_in[1] = 0; }  // earlier windows + own leading flag
-        if (lane == 63 && blockIdx.x == 0) *a.n_parts = sc + 1;
+        if (lane == 63 && blockIdx.x == 0) *a.c.n_parts = sc + 1;
     }
     __syncthreads();
-    const uint32_t add = s_in[0];
-    PAIR_CLK(9);
-    for (uint32_t j = tid; j < M; j += 1024) {
-        a.part_id[start + j] = add + ID[j];
-        a.perm[start + j] = I(src)[j];
+    return s_in[0];
+}
+
+// output: the window's M places of the sorted order begin at `start`
+__device__ __forceinline__ void window_output(const SingleArgs& a, uint32_t start, uint32_t add, const uint32_t* ID,
+                                              const uint32_t* sorted, uint32_t M) {
+    for (uint32_t j = threadIdx.x; j < M; j += 1024) {
+        a.c.part_id[start + j] = add + ID[j];
+        a.c.perm[start + j] = sorted[j];
     }
+}
+
+template <bool LDS>
+__device__ __forceinline__ void window_work(const SingleArgs& a, char* s_dyn, uint32_t* s_cnt, uint32_t* s_w,
+                                            const uint32_t* s_soff, const uint32_t* s_scnt, uint32_t lo, uint32_t hi,
+                                            uint32_t start, uint32_t M, uint32_t low_bits) {
+    // both halves of a ping-pong pair hang off one base pointer (LDS or HBM scratch): half h is base + h * stride
+    uint64_t* const kbase = LDS ? reinterpret_cast<uint64_t*>(s_dyn) : a.gkey + start;
+    uint32_t* const ibase = LDS ? reinterpret_cast<uint32_t*>(s_dyn + 2 * kWinCap * 8) : a.gidx + start;
+    const uint32_t stride = LDS ? kWinCap : a.c.n;
+    auto K = [&](int h) { return kbase + (size_t)h * stride; };
+    auto I = [&](int h) { return ibase + (size_t)h * stride; };
+    window_gather(a, s_soff, s_scnt, lo, hi, low_bits, K(0), I(0));
+    PAIR_CLK(5);
+    int src = 0;
+    bool sorted = false;
+    if constexpr (LDS) sorted = window_merge_runs(K, I, M, s_w, &src);
+    if (!sorted) window_count_passes(K, I, M, s_cnt, s_w, lo, hi, low_bits, &src);
+    PAIR_CLK(6);
+    uint32_t* ID = I(src ^ 1);  // the free index buffer
+    const uint32_t flags = window_local_ids<LDS>(a, K(src), ID, M, s_w);
+    if (threadIdx.x == 0) {
+        agent_store(a.win + 2 * blockIdx.x, flags);
+        agent_store(a.win + 2 * blockIdx.x + 1, M);
+        agent_store(a.win_keys + 2 * blockIdx.x, K(src)[0]);
+        agent_store(a.win_keys + 2 * blockIdx.x + 1, K(src)[M - 1]);
+    }
+    PAIR_CLK(7);
+    if (!grid_barrier(a.counter + 1, nullptr, a.c.note)) return;
+    PAIR_CLK(8);
+    const uint32_t add = window_table(a);
+    PAIR_CLK(9);
+    window_output(a, start, add, ID, I(src), M);
     PAIR_CLK(10);
 }
 
@@ -788,13 +785,13 @@ __global__ __launch_bounds__(1024) void k_pair_single(SingleArgs a) {
     PAIR_CLK(0);
     // ---- slice pass
     {
-        const uint32_t sl = g * a.slice_len, sh = min(a.n, sl + a.slice_len);
+        const uint32_t sl = g * a.slice_len, sh = min(a.c.n, sl + a.slice_len);
         for (uint32_t base = sl + wave * 64; base < sh; base += 1024) {
             const uint32_t i = base + lane;
             const bool valid = i < sh;
             uint32_t fine = ~0u;
             if (valid) {
-                const uint64_t d = dense_key(a.f, a.keys[i]);
+                const uint64_t d = dense_key(a.c.f, a.keys[i]);
                 agent_store(a.dense + i, d);
                 fine = (uint32_t)(d >> low_bits);
             }
@@ -807,7 +804,7 @@ __global__ __launch_bounds__(1024) void k_pair_single(SingleArgs a) {
         if (tid < (int)kFine) agent_store(a.rows + (size_t)g * kFine + tid, incl);
     }
     PAIR_CLK(1);
-    if (!grid_barrier(a.counter, a.counter_stale, a.note)) return;
+    if (!grid_barrier(a.counter, a.counter_stale, a.c.note)) return;
     PAIR_CLK(2);
     // ---- windows: column sums of the prefix rows = keys in buckets 0..b over all slices (every load of a
     // thread in flight at once: thread t sums bucket t % 512 over one half of the slices)
@@ -839,7 +836,7 @@ __global__ __launch_bounds__(1024) void k_pair_single(SingleArgs a) {
     PAIR_CLK(3);
     if (M == 0) {  // no bucket starts inside this window's stretch
         if (tid == 0) { agent_store(a.win + 2 * g, 0u); agent_store(a.win + 2 * g + 1, 0u); }
-        (void)grid_barrier(a.counter + 1, nullptr, a.note);
+        (void)grid_barrier(a.counter + 1, nullptr, a.c.note);
         return;
     }
     // every slice's share of the window and where it goes
@@ -850,13 +847,7 @@ __global__ __launch_bounds__(1024) void k_pair_single(SingleArgs a) {
             const uint32_t below = lo ? agent_load(a.rows + (size_t)lane * kFine + lo - 1) : 0u;
             c = upto - below;
         }
-        uint32_t sc = c;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t t = __shfl_up(sc, k);
-            if (lane >= k) sc += t;
-        }
-        s_soff[lane] = sc - c;
+        s_soff[lane] = wave_scan(c, OpAdd32()) - c;
         s_scnt[lane] = c;
     }
     __syncthreads();
@@ -898,6 +889,13 @@ KeyFields fields_of(uint64_t bits, uint32_t* live) {
     return f;
 }
 
+// the call's part of the last kernel's arguments, on every plan; after svx_ws_lay, which may move the workspace
+PairCall pair_call(const svx_ctx* ctx, const KeyFields& f, uint32_t n, uint32_t max_dist, uint32_t* d_perm, uint32_t* d_part_id,
+                   uint32_t* d_n_parts) {
+    uint32_t* note = reinterpret_cast<uint32_t*>(ctx->ws) + SVX_WS_BARRIER_NOTE_WORD;
+    return PairCall{f, n, max_dist, d_perm, d_part_id, d_n_parts, note};
+}
+
 int pair_single_launch(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_t max_dist, const KeyFields& f,
                        uint32_t live, uint32_t* d_perm, uint32_t* d_part_id, uint32_t* d_n_parts) {
     if (!ctx->pair_lds_set) {  // once per context: the attribute is kept per device
@@ -921,17 +919,11 @@ int pair_single_launch(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32_
     ws.add(&a.win_keys, 2 * grid);
     SVX_TRY(svx_ws_lay(ctx, ws));
     a.keys = d_keys;
-    a.f = f;
-    a.n = n;
+    a.c = pair_call(ctx, f, n, max_dist, d_perm, d_part_id, d_n_parts);
     a.live = live;
-    a.max_dist = max_dist;
-    a.perm = d_perm;
-    a.part_id = d_part_id;
-    a.n_parts = d_n_parts;
     // workspace header, words 68..71: two sets of two arrival counters, alternate launches alternate sets
-    a.counter = reinterpret_cast<uint32_t*>(ctx->ws) + 68 + 2 * (ctx->pair_launches & 1u);
-    a.counter_stale = reinterpret_cast<uint32_t*>(ctx->ws) + 68 + 2 * ((ctx->pair_launches & 1u) ^ 1u);
-    a.note = reinterpret_cast<uint32_t*>(ctx->ws) + kBarrierNoteWord;
+    a.counter = reinterpret_cast<uint32_t*>(ctx->ws) + SVX_WS_SINGLE_COUNTERS_WORD + 2 * (ctx->pair_launches & 1u);
+    a.counter_stale = reinterpret_cast<uint32_t*>(ctx->ws) + SVX_WS_SINGLE_COUNTERS_WORD + 2 * ((ctx->pair_launches & 1u) ^ 1u);
     SVX_TRY(svx_timing_begin(ctx));
     SVX_TRY(svx_timing_mark(ctx, 1));
     hipLaunchKernelGGL(k_pair_single, dim3(grid), dim3(1024), kSingleDynLds, ctx->stream, a);
@@ -988,14 +980,9 @@ int pair_partition_bits(svx_ctx* ctx, const uint64_t* d_keys, uint32_t n, uint32
     PartArgs pa;
     pa.sorted_keys = b.keys[b.passes & 1];
     pa.sorted = b.idx[b.passes & 1];
-    pa.f = b.f;
-    pa.n = n;
-    pa.max_dist = max_dist;
-    pa.perm = d_perm;
-    pa.part_id = d_part_id;
-    pa.n_parts = d_n_parts;
+    pa.c = pair_call(ctx, b.f, n, max_dist, d_perm, d_part_id, d_n_parts);
     pa.block_tot = block_tot;
-    pa.counter = reinterpret_cast<uint32_t*>(ctx->ws) + 64;  // workspace header: zero between calls
+    pa.counter = reinterpret_cast<uint32_t*>(ctx->ws) + SVX_WS_SWEEP_COUNTERS_WORD;
     const uint32_t span = ((n + part_grid - 1) / part_grid + 1023) / 1024 * 1024;
     if (ctx->pair_wait_free) {
         hipLaunchKernelGGL(k_partition<1>, dim3((n + span - 1) / span), dim3(1024), 0, ctx->stream, pa, span);
