@@ -920,6 +920,54 @@ int svx_indel_shift(svx_ctx* ctx, const uint8_t* bases, uint64_t n_bases, const 
 #define SVX_SHIFT_LANE_STEPS 8
 int svx_ctx_set_shift_lane_steps(svx_ctx* ctx, int32_t steps);
 
+/*
+ * Haplotype replay, batched: which string do a job's edits make of its reference window, and are two such strings the
+ * same?  `bases` is ONE pool of n_bases bytes that holds the windows and the alternative alleles; the entry compares bytes
+ * as they are (a caller that wants case ignored hands over one case).  Job j < n_jobs is the window bases[win_off[j] ..
+ * win_off[j] + win_len[j]) with the edits ed_first[j] .. ed_first[j + 1] - 1 (n_jobs + 1 entries, ed_first[0] == 0), taken
+ * in the given order; edit e replaces the ed_ref_len[e] window bytes from ed_start[e] on (relative to the window) by
+ * bases[ed_alt_off[e] .. ed_alt_off[e] + ed_alt_len[e]).  Pair k < n_pairs names two jobs.  The definition is this loop:
+ *     p = 0;  string = "";  order = inside = true
+ *     for every edit e of job j, in the given order:
+ *         order  = false unless ed_start[e] >= p, and, for e not the job's first, ed_start[e] > ed_start[e - 1]
+ *         inside = false unless ed_start[e] + ed_ref_len[e] <= win_len[j]
+ *         string += win[p : ed_start[e]] + alt(e)
+ *         p = ed_start[e] + ed_ref_len[e]
+ *     string += win[p : win_len[j]]
+ *     status[j]  = 1 unless order, else 2 unless inside, else 0
+ *     out_len[j] = len(string) where status[j] == 0, else 0 (and the job has no string)
+ *     equal[k]   = 1 iff status[pair_a[k]] == status[pair_b[k]] == 0 and both strings have equal lengths and equal bytes
+ * So two edits at one start and an edit that begins inside the one before it are out of order; an edit that begins exactly
+ * where the one before it ends is in order; a job paired with itself and two empty strings are equal.  Every output
+ * depends on its own job or pair alone and is identical from run to run.
+ * Strings: with out != NULL the strings of all jobs, one behind the other in job order, go to `out` and their offsets to
+ * out_off (n_jobs + 1 entries; may be NULL); `cap` / `n_out` as for svx_cigar_extract: *n_out (may be NULL) always receives
+ * the exact total, min(total, cap) bytes are written, SVX_E_CAPACITY beyond cap.  With out == NULL the strings stay in the
+ * workspace, cap is ignored, and out_off and n_out are still served.
+ * All pointers are HOST pointers; the call returns with the outputs written.  SVX_E_INVALID — nothing launched, the context
+ * usable, the message names the job, the edit or the pair — for ed_first[0] != 0, a decreasing ed_first, ed_first[n_jobs]
+ * != n_edits, a window or an alternative allele that ends behind n_bases, a pair index >= n_jobs, and a null pointer where
+ * a count is positive.  n_jobs == 0, n_pairs == 0, jobs without edits and windows of length 0 are valid.  SVX_E_TOO_LARGE
+ * when the windows plus the alternative alleles of one call (the sum of all win_len and all ed_alt_len, which no total
+ * exceeds) pass SVX_REPLAY_MAX_BYTES — the output offsets are 32 bits wide —, or when the pairs' strings (for each pair the
+ * shorter member, bounded the same way) pass 2^31 - 1 tiles.
+ * Count, scan, emit: one scan over the edits for the bytes in front of each and for the status, one over the jobs for the
+ * offsets, then a workgroup per tile of SVX_REPLAY_TILE consecutive OUTPUT BYTES of the whole call, 16 per lane — bytes
+ * are dealt out, not jobs —; the pairs' bytes are dealt out the same way and a lane that sees a difference clears the flag.
+ * No atomics; twelve launches at most (svim_asm_amd/csrc/svx_replay.hip lists them).
+ * Measured once (2026-10-21, one MI355X, tools/replay_probe.py, synthetic: 10^6 phased clusters, 4 * 10^6 jobs and pairs,
+ * 2.65 * 10^6 edits, a pool of 101 MB, 393 MB of strings): the call 17.5 ms on a host clock, of which the kernels 1.67 ms
+ * (emit and compare 1.44), the uploads alone 4.5 ms (a quarter), and the rest the host's checks over every job, edit and
+ * pair, the read-backs and the binding; the plain splice in numpy, one thread: 2.9 s.  DESIGN.md 3.20.
+ */
+#define SVX_REPLAY_TILE 4096
+#define SVX_REPLAY_MAX_BYTES 0xFFFFF000ull
+int svx_variant_replay(svx_ctx* ctx, const uint8_t* bases, uint64_t n_bases, const uint64_t* win_off, const uint32_t* win_len,
+                       const uint32_t* ed_first, uint32_t n_jobs, const uint32_t* ed_start, const uint32_t* ed_ref_len,
+                       const uint64_t* ed_alt_off, const uint32_t* ed_alt_len, uint32_t n_edits, const uint32_t* pair_a,
+                       const uint32_t* pair_b, uint32_t n_pairs, uint32_t* out_len, uint8_t* status, uint8_t* equal, uint8_t* out,
+                       uint32_t* out_off, uint64_t cap, uint64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

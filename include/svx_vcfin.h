@@ -90,6 +90,70 @@ int svx_vcfin_open_sites(const char* path, int32_t n_ref, const char* const* nam
 int svx_vcfin_get_columns(const svx_vcfin* v, svx_vcfin_columns* out);
 void svx_vcfin_close(svx_vcfin* v);
 
+/*
+ * THE SAME FILE AS A LIST OF EDITS (svx_vcfin_open_alleles, svx_vcfin_get_alleles): every sequence-resolved record of one
+ * sample — SNVs, MNPs, small and large indels, replacements — as "these reference bytes become those bytes", which is what
+ * svim-asm-small-compare replays.  File handling, header, line ends, the genotype rule and the refusals
+ * are those of svx_vcfin_open; a record's REF may reach to the contig's end and no further.
+ *
+ * CLASSIFICATION.  Every data line falls into exactly one class; the first rule of this list that applies decides:
+ *   filtered           with `passonly`: FILTER is neither PASS nor "."
+ *   multiallelic       ALT contains ','
+ *   symbolic_or_other  REF or ALT is not a string over letters ("" and "." count as the empty string): <DEL>, <INS>,
+ *                      breakends, "*", ...
+ *   no_change          REF and ALT are the same string without regard to case: the edit is empty
+ *   not_carried        the sample's GT carries no allele 1
+ *   row                everything else.  Both alleles in upper case, p the length of their longest common prefix and s the
+ *                      length of the longest common suffix of what is left behind it (prefix first: the rule that makes a
+ *                      deletion [POS-1+p, ..) and an insertion lie at POS-1+p above):
+ *                          start = POS-1+p    ref_len = len(REF)-p-s    alt = ALT[p : len(ALT)-s]
+ * `phased` is 1 when the GT's first separator is '|', when the GT has one allele, when both alleles are 1, and when the
+ * file has no genotype for the record (no sample columns or a FORMAT that does not start with GT: gt is 0, unknown, and
+ * the record counts as carried on both haplotypes); 0 otherwise (0/1, ./1).
+ */
+enum {
+    SVX_VCFIN_A_ROW = 0,
+    SVX_VCFIN_A_MULTIALLELIC = 1,
+    SVX_VCFIN_A_SYMBOLIC_OR_OTHER = 2,
+    SVX_VCFIN_A_NOT_CARRIED = 3,
+    SVX_VCFIN_A_FILTERED = 4,
+    SVX_VCFIN_A_NO_CHANGE = 5,
+    SVX_VCFIN_A_N_CLASSES = 6
+};
+
+/* Everything points into the handle and lives as long as it.  Rows are in file order. */
+typedef struct svx_vcfin_alleles {
+    uint64_t n;
+    const int32_t* contig;        /* index into the names given to svx_vcfin_open_alleles */
+    const int64_t* start;         /* the reference bytes [start, start + ref_len) become alts[alt_off .. alt_off + alt_len) */
+    const uint32_t* ref_len;
+    const uint64_t* alt_off;
+    const uint32_t* alt_len;
+    const uint8_t* alts;          /* upper case */
+    uint64_t alt_bytes;
+    const int64_t* pos;           /* POS - 1: where the REF column as written begins on the contig */
+    const uint64_t* ref_off;      /* the REF column as written, in `text` ("." has length 0) */
+    const uint32_t* ref_text_len;
+    const uint8_t* gt;            /* haplotype bits 1 | 2; 0: unknown — the record is CARRIED ON BOTH haplotypes (phased is 1):
+                                   * a caller that deals records out by bit has to read 0 as 3, as svim-asm-small-compare does */
+    const uint8_t* phased;
+    const uint64_t* line_off;     /* as in svx_vcfin_columns */
+    const uint32_t* line_len;
+    const uint32_t* line_no;
+    const uint64_t* id_off;
+    const uint32_t* id_len;
+    const char* text;
+    uint64_t text_bytes;
+    uint64_t header_bytes;
+    uint64_t n_lines;
+    uint64_t counts[SVX_VCFIN_A_N_CLASSES];
+} svx_vcfin_alleles;
+
+int svx_vcfin_open_alleles(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
+                           int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap);
+/* SVX_E_INVALID for a handle that svx_vcfin_open_alleles did not make (and svx_vcfin_get_columns for one that it made). */
+int svx_vcfin_get_alleles(const svx_vcfin* v, svx_vcfin_alleles* out);
+
 #ifdef __cplusplus
 }
 #endif

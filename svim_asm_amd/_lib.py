@@ -116,6 +116,15 @@ class VcfinColumns(C.Structure):
                 ("header_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("counts", C.c_uint64 * 8)]
 
 
+class VcfinAlleles(C.Structure):
+    """svx_vcfin_alleles (include/svx_vcfin.h)."""
+    _fields_ = [("n", C.c_uint64), ("contig", C.c_void_p), ("start", C.c_void_p), ("ref_len", C.c_void_p), ("alt_off", C.c_void_p),
+                ("alt_len", C.c_void_p), ("alts", C.c_void_p), ("alt_bytes", C.c_uint64), ("pos", C.c_void_p), ("ref_off", C.c_void_p),
+                ("ref_text_len", C.c_void_p), ("gt", C.c_void_p), ("phased", C.c_void_p), ("line_off", C.c_void_p),
+                ("line_len", C.c_void_p), ("line_no", C.c_void_p), ("id_off", C.c_void_p), ("id_len", C.c_void_p), ("text", C.c_void_p),
+                ("text_bytes", C.c_uint64), ("header_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("counts", C.c_uint64 * 6)]
+
+
 class CollectOut(C.Structure):
     """svx_collect_out (include/svx.h)."""
     _fields_ = [("sig", SigSoa), ("sig_cap", C.c_uint64), ("n_sig", C.c_uint64), ("raw", C.c_void_p),
@@ -134,6 +143,8 @@ MISMATCH_TILE = 4096             # SVX_MISMATCH_TILE: reference positions of one
 SHIFT_WAVE_COLS = 256            # SVX_SHIFT_WAVE_COLS: steps one iteration of indel_shift's wave form tests
 SHIFT_LANE_STEPS = 8             # SVX_SHIFT_LANE_STEPS: steps of indel_shift's lane form before the hand-over (default)
 SHIFT_LANES_ONLY = 0x7FFFFFFF    # set_shift_lane_steps: every event stays in the lane form
+REPLAY_TILE = 4096               # SVX_REPLAY_TILE: output bytes of the whole call per workgroup of variant_replay
+REPLAY_MAX_BYTES = 0xFFFFF000    # SVX_REPLAY_MAX_BYTES: most window plus alternative bytes of one variant_replay
 COVER_SCAN_CHUNK = 1024  # SVX_COVER_SCAN_CHUNK: entries of a list the prefix-maximum scan of cover_query takes per pass
 LINKAGE_LANES_ONLY = 0xFFFFFFFF  # set_linkage_group_min: every partition down the lane path
 MATCH_LDS_PAIRS = 32768          # SVX_MATCH_LDS_PAIRS: largest matrix the matching group kernel keeps in LDS
@@ -219,6 +230,8 @@ SYMBOLS = {
                                          C.c_uint64, C.POINTER(C.c_uint64)]),
     "svx_indel_shift": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     "svx_ctx_set_shift_lane_steps": (C.c_int, [_P, C.c_int32]),
+    "svx_variant_replay": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P,
+                                     _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     # native BAM ingest (include/svx_bam.h)
     "svx_bam_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_bam_close": (None, [_P]),
@@ -251,6 +264,8 @@ SYMBOLS = {
     "svx_vcfin_open_sites": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_int, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "svx_vcfin_get_columns": (C.c_int, [_P, C.POINTER(VcfinColumns)]),
     "svx_vcfin_close": (None, [_P]),
+    "svx_vcfin_open_alleles": (C.c_int, [C.c_char_p, C.c_int32, _P, _P, C.c_char_p, C.c_int, C.c_int, C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "svx_vcfin_get_alleles": (C.c_int, [_P, C.POINTER(VcfinAlleles)]),
     # the CIGAR-text parsers (include/svx_sam.h)
     "svx_cigar_text_parse": (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.c_int]),
     "svx_cigar_text_parse_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P]),
@@ -943,6 +958,53 @@ class Context:
         self._check(self.lib.svx_indel_shift(self.h, _ptr(bases), len(bases), _ptr(ref_off), _ptr(ref_len), _ptr(qry_off),
                                              _ptr(qry_len), _ptr(ref_start), n_aln, *[_ptr(x) for x in ev], n_ev, _ptr(shift)))
         return shift
+
+    def variant_replay(self, bases, win_off, win_len, ed_first, ed_start, ed_ref_len, ed_alt_off, ed_alt_len, pair_a=(), pair_b=(),
+                       strings=False, cap=None):
+        """The haplotype strings that lists of edits make of reference windows, and which pairs of them are the same
+        (svx_variant_replay in include/svx.h).  `bases`: one uint8 pool with job j's window at win_off[j] (win_len[j]
+        bytes) and edit e's alternative bytes at ed_alt_off[e] (ed_alt_len[e] bytes); job j's edits are ed_first[j] ..
+        ed_first[j + 1] - 1, with ed_start relative to the window; a pair is two job indices.  Returns dict(out_len:
+        uint32, status: uint8 per job; equal: uint8 per pair; total: the bytes of all strings), and with `strings` also
+        out (uint8) and out_off (uint32, one entry more than jobs).  `cap`: bytes of `out` to offer (default: all windows
+        plus all alternative bytes, which no total exceeds: ONE call); fewer than the total raise SvxError(SVX_E_CAPACITY)
+        with `total` and the written bytes in the error's `partial`."""
+        bases = _as(bases, np.uint8)
+        win_off, win_len = _as(win_off, np.uint64), _as(win_len, np.uint32)
+        ed_first = _as(ed_first, np.uint32)
+        n_jobs = len(win_off)
+        if len(win_len) != n_jobs or len(ed_first) != n_jobs + 1:
+            raise SvxError(SVX_E_INVALID, "one win_off and win_len per job, one ed_first more than jobs")
+        ed = [_as(ed_start, np.uint32), _as(ed_ref_len, np.uint32), _as(ed_alt_off, np.uint64), _as(ed_alt_len, np.uint32)]
+        n_edits = len(ed[0])
+        if any(len(x) != n_edits for x in ed):
+            raise SvxError(SVX_E_INVALID, "one ed_start, ed_ref_len, ed_alt_off and ed_alt_len per edit")
+        pair_a, pair_b = _as(pair_a, np.uint32), _as(pair_b, np.uint32)
+        n_pairs = len(pair_a)
+        if len(pair_b) != n_pairs:
+            raise SvxError(SVX_E_INVALID, "one pair_b per pair_a")
+        res = {"out_len": np.zeros(n_jobs, np.uint32), "status": np.zeros(n_jobs, np.uint8), "equal": np.zeros(n_pairs, np.uint8)}
+        head = (self.h, _ptr(bases), len(bases), _ptr(win_off), _ptr(win_len), _ptr(ed_first), n_jobs, *[_ptr(x) for x in ed], n_edits,
+                _ptr(pair_a), _ptr(pair_b), n_pairs, _ptr(res["out_len"]), _ptr(res["status"]), _ptr(res["equal"]))
+        n = C.c_uint64(0)
+        if not strings:
+            self._check(self.lib.svx_variant_replay(*head, None, None, 0, C.byref(n)))
+            res["total"] = int(n.value)
+            return res
+        res["out_off"] = np.zeros(n_jobs + 1, np.uint32)
+        if cap is None:
+            cap = int(win_len.sum(dtype=np.uint64)) + int(ed[3].sum(dtype=np.uint64))
+        cap = int(cap)
+        out = np.zeros(max(cap, 1), np.uint8)  # (a valid pointer for cap 0 too)
+        rc = self.lib.svx_variant_replay(*head, _ptr(out), _ptr(res["out_off"]), cap, C.byref(n))
+        res["total"] = int(n.value)
+        res["out"] = out[:min(cap, res["total"])]
+        if rc == SVX_E_CAPACITY:
+            err = SvxError(rc, "variant_replay: %d bytes of strings, %d offered" % (res["total"], cap))
+            err.partial = res
+            raise err
+        self._check(rc)
+        return res
 
     def cover_single(self, start_key, end_key, list_off):
         """The ranges on which exactly ONE entry of a list — and the same one throughout — lies over the reference, per

@@ -1,7 +1,7 @@
 // svx_scan_dev.h — the one place for scan and search on the device (gfx9 family DPP): the wave scan ladder, one workgroup's
 // single-pass prefix (group_before) and its chunked, carried scan over any range (carried_scan), for any value type made
 // of 32-bit words whose all-zero pattern is the operator's identity — unsigned maxima, sums, pairs of them —, and the
-// upper bound among sorted 64-bit keys.  Workgroups of kScanThreads lanes.  Device code only; every translation unit that
+// upper bound among sorted 64- or 32-bit keys.  Workgroups of kScanThreads lanes.  Device code only; every translation unit that
 // includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -113,8 +113,9 @@ __device__ __forceinline__ void carried_scan(uint64_t lo, uint64_t hi, Op op, Lo
     }
 }
 
-// first index in [lo, hi) with p[index] > target, hi when there is none
-__device__ __forceinline__ uint64_t upper_bound(const uint64_t* __restrict__ p, uint64_t lo, uint64_t hi, uint64_t target) {
+// first index in [lo, hi) with p[index] > target, hi when there is none (keys of 64 or of 32 bits)
+template <typename K>
+__device__ __forceinline__ uint64_t upper_bound(const K* __restrict__ p, uint64_t lo, uint64_t hi, uint64_t target) {
     uint64_t n = hi - lo;
     while (n) {
         const uint64_t half = n >> 1;

@@ -27,11 +27,13 @@ namespace {
 using namespace svx_textaln;
 
 struct Row : Line {
-    uint64_t line_end, id_off, seq_off;  // seq_off: the inserted bytes in the text (INS)
-    int64_t start, end;
+    uint64_t line_end, id_off, seq_off;  // seq_off: the inserted bytes in the text (INS; the alleles reader: the alternative bytes)
+    int64_t start, end;                  // (the alleles reader: end = POS - 1)
     int32_t contig;
     uint32_t id_len, seq_len;
-    uint8_t cls, gt;
+    uint64_t ref_off;                    // the alleles reader: the REF column in the text, as written
+    uint32_t ref_text_len, ref_len;
+    uint8_t cls, gt, phased;
 };
 
 struct Dict {
@@ -84,11 +86,19 @@ uint8_t genotype_bits(const char* s, uint64_t n) {
     return bits;
 }
 
+// is the GT text [s, s + n) with the bits above phased?  its first separator is '|', it has one allele, or both alleles are 1
+uint8_t genotype_phased(const char* s, uint64_t n, uint8_t bits) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (s[i] == '/' || s[i] == '|') return s[i] == '|' || bits == 3;
+    return 1;
+}
+
 struct Classifier {
     const char* m;
     const Dict* dict;
     int sample_col;  // column of the chosen sample (>= 9), -1: the file has no sample columns
     bool passonly;
+    bool alleles;    // svx_vcfin_open_alleles: the classes and the rows of the second reader
 
     // One data line [a, e) (no line end, no '\r'): false with *what set when it is refused.
     bool operator()(uint64_t a, uint64_t e, Row* r, std::string* what) const {
@@ -110,6 +120,7 @@ struct Classifier {
         r->id_off = f[2];
         r->id_len = (uint32_t)std::min<uint64_t>(len(2), 0xFFFFFFFFu);
         r->seq_off = 0; r->seq_len = 0; r->start = 0; r->end = 0; r->gt = 0;
+        r->ref_off = 0; r->ref_text_len = 0; r->ref_len = 0; r->phased = 1;
         const std::string chrom(m + f[0], len(0));
         auto it = dict->tid_of.find(chrom);
         if (it == dict->tid_of.end()) { *what = "the contig '" + chrom.substr(0, 80) + "' is not in the genome's index"; return false; }
@@ -124,9 +135,36 @@ struct Classifier {
         const char* ref = m + f[3];
         const char* alt = m + f[4];
         uint64_t nref = len(3), nalt = len(4);
-        if (passonly && !equals(m + f[6], len(6), "PASS") && !equals(m + f[6], len(6), ".")) { r->cls = SVX_VCFIN_FILTERED; return true; }
-        if (memchr(alt, ',', nalt)) { r->cls = SVX_VCFIN_MULTIALLELIC; return true; }
+        if (passonly && !equals(m + f[6], len(6), "PASS") && !equals(m + f[6], len(6), ".")) {
+            r->cls = alleles ? SVX_VCFIN_A_FILTERED : SVX_VCFIN_FILTERED;
+            return true;
+        }
+        if (memchr(alt, ',', nalt)) { r->cls = alleles ? SVX_VCFIN_A_MULTIALLELIC : SVX_VCFIN_MULTIALLELIC; return true; }
         if (equals(ref, nref, ".")) nref = 0;
+        if (alleles) {
+            if (equals(alt, nalt, ".")) nalt = 0;
+            if (!all_letters(ref, nref) || !all_letters(alt, nalt)) { r->cls = SVX_VCFIN_A_SYMBOLIC_OR_OTHER; return true; }
+            uint64_t p = 0, s = 0;
+            const uint64_t lim = std::min(nref, nalt);
+            while (p < lim && upper(ref[p]) == upper(alt[p])) ++p;
+            while (s < lim - p && upper(ref[nref - 1 - s]) == upper(alt[nalt - 1 - s])) ++s;
+            if (p == nref && p == nalt) { r->cls = SVX_VCFIN_A_NO_CHANGE; return true; }
+            if (nref > 0xFFFFFFFFull || nalt > 0xFFFFFFFFull) { *what = "an allele longer than 4 GiB"; return false; }
+            r->cls = SVX_VCFIN_A_ROW;
+            r->end = (int64_t)pos - 1;
+            r->start = (int64_t)(pos - 1 + p);
+            r->ref_off = f[3];
+            r->ref_text_len = (uint32_t)nref;
+            r->ref_len = (uint32_t)(nref - p - s);
+            r->seq_off = f[4] + p;
+            r->seq_len = (uint32_t)(nalt - p - s);
+            if ((int64_t)(pos - 1 + nref) > clen) {
+                *what = "REF ends at " + std::to_string(pos - 1 + nref) + ", beyond the length of '" + chrom.substr(0, 80) + "' (" +
+                        std::to_string(clen) + ")";
+                return false;
+            }
+            return carried(f[8], e, r, what, SVX_VCFIN_A_NOT_CARRIED);
+        }
         const bool symbolic_del = equals(alt, nalt, "<DEL>");
         if (equals(alt, nalt, ".")) nalt = 0;
         if (symbolic_del) {
@@ -188,9 +226,13 @@ struct Classifier {
                 return true;
             }
         }
-        // a DEL or an INS: is it carried?
+        return carried(f[8], e, r, what, SVX_VCFIN_NOT_CARRIED);
+    }
+
+    // A row's genotype from the sample column of the line that ends at e, `at` the start of FORMAT (column 8): gt, phased,
+    // and the class `not_carried` where the GT carries no allele 1.
+    bool carried(uint64_t at, uint64_t e, Row* r, std::string* what, uint8_t not_carried) const {
         if (sample_col < 0) return true;
-        at = f[8];  // the start of FORMAT (column 8)
         uint64_t fmt = 0, fmt_len = 0;
         for (int k = 8;; ++k) {
             if (at > e) { *what = "the line has no column for the sample"; return false; }
@@ -201,8 +243,10 @@ struct Classifier {
                 // (a FORMAT that does not start with GT: no genotype, the record counts as carried)
                 if (!(fmt_len >= 2 && m[fmt] == 'G' && m[fmt + 1] == 'T' && (fmt_len == 2 || m[fmt + 2] == ':'))) return true;
                 const char* colon = (const char*)memchr(m + at, ':', fe - at);
-                r->gt = genotype_bits(m + at, colon ? (uint64_t)(colon - (m + at)) : fe - at);
-                if (!r->gt) r->cls = SVX_VCFIN_NOT_CARRIED;
+                const uint64_t gn = colon ? (uint64_t)(colon - (m + at)) : fe - at;
+                r->gt = genotype_bits(m + at, gn);
+                r->phased = genotype_phased(m + at, gn, r->gt);
+                if (!r->gt) r->cls = not_carried;
                 return true;
             }
             at = fe + 1;
@@ -221,6 +265,13 @@ struct svx_vcfin {
     std::vector<int64_t> start, end;
     std::vector<uint64_t> seq_off, line_off, id_off;
     std::vector<uint32_t> seq_len, line_len, line_no, id_len;
+    // svx_vcfin_open_alleles: rows of svx_vcfin_alleles (start, contig, gt, seqs / seq_off / seq_len and the line columns above are shared)
+    bool alleles = false;
+    uint64_t acounts[SVX_VCFIN_A_N_CLASSES] = {};
+    std::vector<int64_t> pos;
+    std::vector<uint64_t> ref_off;
+    std::vector<uint32_t> ref_len, ref_text_len;
+    std::vector<uint8_t> phased;
 };
 
 namespace {
@@ -284,7 +335,7 @@ int inflate_bgzf(svx_vcfin* v, const char* path, int n_threads, std::string* err
 
 // svx_vcfin_open, or with `sites` svx_vcfin_open_sites: the sample columns are not looked at
 static int open_vcf(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample, bool sites,
-                    int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
+                    bool alleles, int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
     svx_vcfin* v = nullptr;
     auto refuse = [&](int rc, const std::string& msg) {
         delete v;
@@ -359,13 +410,18 @@ static int open_vcf(const char* path, int32_t n_ref, const char* const* names, c
     // ---- the records
     std::vector<Row> rows;
     std::string msg;
-    const Classifier classify{map, &dict, sample_col, passonly != 0};
+    const Classifier classify{map, &dict, sample_col, passonly != 0, alleles};
+    v->alleles = alleles;
     if (!scan_lines(v->file, at, n_before, threads, classify, &rows, &msg)) return bail(std::string(path) + ": " + msg);
     v->n_lines = rows.size();
     uint64_t n = 0, seq_bytes = 0;
+    const uint8_t last_row_class = alleles ? SVX_VCFIN_A_ROW : SVX_VCFIN_INS;
     for (const Row& r : rows) {
-        ++v->counts[r.cls];
-        if (r.cls <= SVX_VCFIN_INS) { ++n; seq_bytes += r.seq_len; }
+        ++(alleles ? v->acounts : v->counts)[r.cls];
+        if (r.cls <= last_row_class) { ++n; seq_bytes += r.seq_len; }
+    }
+    if (alleles) {
+        v->pos.reserve(n); v->ref_off.reserve(n); v->ref_len.reserve(n); v->ref_text_len.reserve(n); v->phased.reserve(n);
     }
     v->type.reserve(n); v->gt.reserve(n); v->contig.reserve(n); v->start.reserve(n); v->end.reserve(n);
     v->seq_off.reserve(n); v->seq_len.reserve(n); v->line_off.reserve(n); v->line_len.reserve(n); v->line_no.reserve(n);
@@ -373,7 +429,11 @@ static int open_vcf(const char* path, int32_t n_ref, const char* const* names, c
     v->seqs.resize(seq_bytes);
     uint64_t q = 0;
     for (const Row& r : rows) {
-        if (r.cls > SVX_VCFIN_INS) continue;
+        if (r.cls > last_row_class) continue;
+        if (alleles) {
+            v->pos.push_back(r.end); v->ref_off.push_back(r.ref_off); v->ref_len.push_back(r.ref_len);
+            v->ref_text_len.push_back(r.ref_text_len); v->phased.push_back(r.phased);
+        }
         v->type.push_back(r.cls); v->gt.push_back(r.gt); v->contig.push_back(r.contig);
         v->start.push_back(r.start); v->end.push_back(r.end);
         v->seq_off.push_back(q); v->seq_len.push_back(r.seq_len);
@@ -390,16 +450,16 @@ static int open_vcf(const char* path, int32_t n_ref, const char* const* names, c
 
 extern "C" int svx_vcfin_open(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
                               int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
-    return open_vcf(path, n_ref, names, lengths, sample, false, passonly, n_threads, out, err, err_cap);
+    return open_vcf(path, n_ref, names, lengths, sample, false, false, passonly, n_threads, out, err, err_cap);
 }
 
 extern "C" int svx_vcfin_open_sites(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, int passonly,
                                     int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
-    return open_vcf(path, n_ref, names, lengths, nullptr, true, passonly, n_threads, out, err, err_cap);
+    return open_vcf(path, n_ref, names, lengths, nullptr, true, false, passonly, n_threads, out, err, err_cap);
 }
 
 extern "C" int svx_vcfin_get_columns(const svx_vcfin* v, svx_vcfin_columns* out) {
-    if (!v || !out) return SVX_E_INVALID;
+    if (!v || !out || v->alleles) return SVX_E_INVALID;
     out->n = v->type.size();
     out->type = v->type.data(); out->contig = v->contig.data(); out->start = v->start.data(); out->end = v->end.data();
     out->gt = v->gt.data(); out->seq_off = v->seq_off.data(); out->seq_len = v->seq_len.data();
@@ -408,6 +468,25 @@ extern "C" int svx_vcfin_get_columns(const svx_vcfin* v, svx_vcfin_columns* out)
     out->id_off = v->id_off.data(); out->id_len = v->id_len.data();
     out->text = v->file.map; out->text_bytes = v->file.size; out->header_bytes = v->header_bytes; out->n_lines = v->n_lines;
     memcpy(out->counts, v->counts, sizeof(v->counts));
+    return SVX_OK;
+}
+
+extern "C" int svx_vcfin_open_alleles(const char* path, int32_t n_ref, const char* const* names, const int64_t* lengths, const char* sample,
+                                      int passonly, int n_threads, svx_vcfin** out, char* err, size_t err_cap) {
+    return open_vcf(path, n_ref, names, lengths, sample, false, true, passonly, n_threads, out, err, err_cap);
+}
+
+extern "C" int svx_vcfin_get_alleles(const svx_vcfin* v, svx_vcfin_alleles* out) {
+    if (!v || !out || !v->alleles) return SVX_E_INVALID;
+    out->n = v->start.size();
+    out->contig = v->contig.data(); out->start = v->start.data(); out->ref_len = v->ref_len.data();
+    out->alt_off = v->seq_off.data(); out->alt_len = v->seq_len.data(); out->alts = v->seqs.data(); out->alt_bytes = v->seqs.size();
+    out->pos = v->pos.data(); out->ref_off = v->ref_off.data(); out->ref_text_len = v->ref_text_len.data();
+    out->gt = v->gt.data(); out->phased = v->phased.data();
+    out->line_off = v->line_off.data(); out->line_len = v->line_len.data(); out->line_no = v->line_no.data();
+    out->id_off = v->id_off.data(); out->id_len = v->id_len.data();
+    out->text = v->file.map; out->text_bytes = v->file.size; out->header_bytes = v->header_bytes; out->n_lines = v->n_lines;
+    memcpy(out->counts, v->acounts, sizeof(v->acounts));
     return SVX_OK;
 }
 

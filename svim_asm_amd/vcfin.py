@@ -50,6 +50,60 @@ def read_sites(path, contigs, contig_len, passonly=False, threads=0):
     return _read(path, contigs, contig_len, None, passonly, threads, True)
 
 
+ALLELE_CLASSES = ("rows", "multiallelic", "symbolic_or_other", "not_carried", "filtered", "no_change")
+
+
+class VcfAlleles(object):
+    """What read_alleles returns: the sequence-resolved records of one sample as edits, in file order (columns as numpy
+    arrays; svx_vcfin_alleles in include/svx_vcfin.h).
+      contig, start, ref_len        the reference bytes [start, start + ref_len) of contigs[contig] ...
+      alt_off, alt_len, alts        ... become alts[alt_off : alt_off + alt_len] (uint8, upper case)
+      pos, ref_off, ref_text_len    POS - 1 and the REF column as written, text[ref_off : ref_off + ref_text_len]
+      gt, phased                    haplotype bits (0: unknown) and whether the record's haplotypes are told apart
+      line_off, line_len, line_no, id_off, id_len, text, header, counts, n_lines    as for read_vcf"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return len(self.start)
+
+    def line(self, i):
+        return self.text[int(self.line_off[i]):int(self.line_off[i]) + int(self.line_len[i])]
+
+
+def read_alleles(path, contigs, contig_len, sample=None, passonly=False, threads=0):
+    """Read `path` as a list of edits (svx_vcfin_open_alleles).  Raises VcfFormatError with the reader's message."""
+    lib = _lib.load()
+    names = [c.encode() for c in contigs]
+    name_arr = (C.c_char_p * len(names))(*names)
+    lengths = np.ascontiguousarray(contig_len, dtype=np.int64)
+    h, err = C.c_void_p(), C.create_string_buffer(1024)
+    rc = lib.svx_vcfin_open_alleles(str(path).encode(), len(names), C.cast(name_arr, C.c_void_p), lengths.ctypes.data,
+                                    None if sample is None else str(sample).encode(), 1 if passonly else 0, int(threads), C.byref(h),
+                                    err, len(err))
+    if rc != _lib.SVX_OK:
+        raise VcfFormatError(err.value.decode("utf-8", "replace") or "svx_vcfin_open_alleles failed (%d)" % rc)
+    try:
+        c = _lib.VcfinAlleles()
+        rc = lib.svx_vcfin_get_alleles(h, C.byref(c))
+        if rc != _lib.SVX_OK:
+            raise VcfFormatError("svx_vcfin_get_alleles failed (%d)" % rc)
+        n = int(c.n)
+        text = C.string_at(c.text, int(c.text_bytes)) if c.text_bytes else b""
+        return VcfAlleles(
+            contig=_column(c.contig, n, np.int32), start=_column(c.start, n, np.int64), ref_len=_column(c.ref_len, n, np.uint32),
+            alt_off=_column(c.alt_off, n, np.uint64), alt_len=_column(c.alt_len, n, np.uint32),
+            alts=_column(c.alts, int(c.alt_bytes), np.uint8), pos=_column(c.pos, n, np.int64), ref_off=_column(c.ref_off, n, np.uint64),
+            ref_text_len=_column(c.ref_text_len, n, np.uint32), gt=_column(c.gt, n, np.uint8), phased=_column(c.phased, n, np.uint8),
+            line_off=_column(c.line_off, n, np.uint64), line_len=_column(c.line_len, n, np.uint32),
+            line_no=_column(c.line_no, n, np.uint32), id_off=_column(c.id_off, n, np.uint64), id_len=_column(c.id_len, n, np.uint32),
+            text=text, header=text[:int(c.header_bytes)], counts={name: int(c.counts[k]) for k, name in enumerate(ALLELE_CLASSES)},
+            n_lines=int(c.n_lines))
+    finally:
+        lib.svx_vcfin_close(h)
+
+
 def _read(path, contigs, contig_len, sample, passonly, threads, sites):
     lib = _lib.load()
     names = [c.encode() for c in contigs]
