@@ -8,7 +8,8 @@ out of the replay, where they could only collide with their first).  The compare
 (contig, start), are cut into clusters wherever a record begins more than --cluster_distance behind the largest end so
 far; a cluster with a record that has no twin is replayed on the device: its window [smallest start, largest end) with
 each side's edits, per haplotype when every record of the cluster is phased (four jobs, four pairs, the orientation
-with more equal pairs, straight on a tie), else all of a side's records at once (two jobs, one pair).  ONE
+with more equal pairs, straight on a tie), else all of a side's records at once (two jobs, one pair); an insertion and
+the edit that begins where it stands go down as one edit.  ONE
 _fetch_windows and ONE svx_variant_replay per batch of at most --batch_bases pool bytes, whole clusters per batch.  A
 record is TP iff it has a twin or every haplotype it is carried on (both, where the file has no genotype) agrees.
 Everything works on columns: no Python loop per record."""
@@ -133,12 +134,28 @@ def _replay(R, reference, contigs, options, ctx, alts):
         e_job = cl[e_rec] * 4 + side[e_rec] * 2 + e_hap
         o = np.lexsort((e_rec, e_job))  # (records are in (contig, start) order, file order at equal starts)
         e_rec, e_job = e_rec[o], e_job[o]
+        pool = np.concatenate((win, alt_pool))
+        e_start, e_ref = (R["start"][lo:hi] - R["c_lo"][R["cluster"][lo:hi]])[e_rec], R["ref_len"][lo:hi][e_rec]
+        e_at, e_len = alt_at[e_rec], alt_len[e_rec]
+        # an insertion and the edit that begins where it stands (`..I D..` and a mismatching column behind an insertion are
+        # two records of svim-asm-small with ONE start) are one edit: the inserted bases, then the other's.  Two insertions
+        # at one start stay two edits, and out of order.
+        join = np.zeros(len(e_rec), bool)
+        join[1:] = (e_job[1:] == e_job[:-1]) & (e_start[1:] == e_start[:-1]) & (e_ref[:-1] == 0) & (e_ref[1:] > 0)
+        if join.any():
+            second = np.flatnonzero(join)
+            pool = np.concatenate((pool, _flat(pool, e_at, e_len)))  # every edit's bytes once more, edit by edit: the two lie one behind the other
+            e_at = len(pool) - int(e_len.sum()) + np.cumsum(e_len) - e_len
+            e_at[second], e_len = e_at[second - 1], e_len.copy()
+            e_len[second] += e_len[second - 1]
+            keep = np.ones(len(e_rec), bool)
+            keep[second - 1] = False
+            e_job, e_start, e_ref, e_at, e_len = e_job[keep], e_start[keep], e_ref[keep], e_at[keep], e_len[keep]
         ed_first = np.zeros(4 * k + 1, np.int64)
         np.cumsum(np.bincount(e_job, minlength=4 * k), out=ed_first[1:])
         pa = np.tile(np.array([0, 1, 0, 1]), k) + np.repeat(np.arange(k) * 4, 4)
         pb = np.tile(np.array([2, 3, 3, 2]), k) + np.repeat(np.arange(k) * 4, 4)
-        res = ctx.variant_replay(np.concatenate((win, alt_pool)), np.repeat(win_off[:-1], 4), np.repeat(win_off[1:] - win_off[:-1], 4), ed_first,
-                                 (R["start"][lo:hi] - R["c_lo"][R["cluster"][lo:hi]])[e_rec], R["ref_len"][lo:hi][e_rec], alt_at[e_rec], alt_len[e_rec], pa, pb)
+        res = ctx.variant_replay(pool, np.repeat(win_off[:-1], 4), np.repeat(win_off[1:] - win_off[:-1], 4), ed_first, e_start, e_ref, e_at, e_len, pa, pb)
         status[first:last] = np.asarray(res["status"]).reshape(k, 4)
         equal[first:last] = np.asarray(res["equal"]).reshape(k, 4)
     if (status == 2).any():

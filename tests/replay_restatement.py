@@ -253,8 +253,15 @@ def compare_small(out_dir, base_path, comp_path, ref_seqs, contigs, max_size=50,
         phased = all(r["phased"] for r in cl)
 
         def string(side, h):
-            edits = [(r["start"] - lo, r["ref_len"], r["alt"].encode()) for r in cl
-                     if r["side"] == side and (h is None or (r["gt"] or 3) >> h & 1)]
+            listed = [(r["start"] - lo, r["ref_len"], r["alt"].encode()) for r in cl
+                      if r["side"] == side and (h is None or (r["gt"] or 3) >> h & 1)]
+            edits = []
+            for i, e in enumerate(listed):
+                # an insertion and the edit that begins where it stands are one edit (two insertions there are not)
+                if i and listed[i - 1][1] == 0 and e[1] > 0 and listed[i - 1][0] == e[0]:
+                    edits[-1] = (e[0], e[1], listed[i - 1][2] + e[2])
+                else:
+                    edits.append(e)
             st, s = replay_job(win, edits)
             assert st != NOT_INSIDE
             if st == OUT_OF_ORDER:

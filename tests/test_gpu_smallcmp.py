@@ -5,7 +5,7 @@ import pytest
 
 from svim_asm_amd import smallcmp_cli
 from tests import smallcmp_cases as S
-from tests.test_smallcmp_host import integers
+from tests.test_smallcmp_host import insertion_and_the_edit_where_it_stands, integers
 
 pytestmark = pytest.mark.gpu
 
@@ -48,3 +48,12 @@ def test_d_unphased_comp_takes_the_union(svx_ctx, tmp_path):
 def test_f_several_batches_give_the_same_bytes(svx_ctx, tmp_path):
     summary, _ = S.check(run, *pair(tmp_path), tmp_path, batch_bases=300)
     assert integers(summary) == (929, 0, 929, 0, 846, 83, 846, 83)
+
+
+def test_an_insertion_and_the_edit_where_it_stands_are_one_edit(svx_ctx, tmp_path):
+    base, comp, twice = insertion_and_the_edit_where_it_stands()
+    files = lambda d, body: (S.write(tmp_path / d, "base.vcf", S.HEADER + base), S.write(tmp_path / d, "comp.vcf", S.HEADER + body))
+    summary, _ = S.check(run, *files("once", comp), tmp_path / "once")
+    assert integers(summary) == (2, 0, 4, 0, 0, 2, 0, 4) and summary["comp"]["conflict"] == 0
+    summary, _ = S.check(run, *files("twice", twice), tmp_path / "twice")
+    assert summary["comp"]["conflict"] == 1 and integers(summary)[:4] == (1, 1, 2, 3)

@@ -219,6 +219,25 @@ def test_an_mnp_against_its_two_snvs_and_empty_sides(device, tmp_path):
     assert s["precision"] is None and s["clusters"]["all"] == 0
 
 
+def insertion_and_the_edit_where_it_stands():
+    """(base, comp, comp with a second insertion) as svim-asm-small writes `..I D..` and a mismatching column behind an
+    insertion: two records with one start each; base spells each pair as one complex record."""
+    a, b = S.ref_at(C, 1000, 4), S.ref_at(C, 2000, 2)
+    comp = S.line(C, 1000, a[0], a[0] + "GG", "1|0") + S.line(C, 1000, a, a[0], "1|0")                 # 1000: GG inserted, three bases deleted
+    comp += S.line(C, 2000, b[0], b[0] + "TTT", "0|1") + S.line(C, 2001, b[1], S.other(b[1]), "0|1")  # 2000: TTT inserted in front of an SNV
+    base = S.line(C, 1000, a, a[0] + "GG", "1|0") + S.line(C, 2000, b, b[0] + "TTT" + S.other(b[1]), "0|1")
+    return base, comp, comp + S.line(C, 1000, a[0], a[0] + "C", "1|0", rid="second")
+
+
+def test_an_insertion_and_the_edit_where_it_stands_are_one_edit(device, tmp_path):
+    base, comp, twice = insertion_and_the_edit_where_it_stands()
+    s = made_up(tmp_path, base, comp)
+    assert integers(s) == (2, 0, 4, 0, 0, 2, 0, 4) and s["comp"]["conflict"] == s["base"]["conflict"] == 0
+    assert s["clusters"]["replayed"] == 2 and CALLS == {"variant_replay": 1, "jobs": 8}
+    s = made_up(tmp_path / "twice", base, twice)     # two insertions at one start: out of order, as before
+    assert s["comp"]["conflict"] == 1 and integers(s)[:4] == (1, 1, 2, 3)
+
+
 # ------------------------------------------------------------------------------------------------- exit statuses
 def test_g_exit_codes_and_help(device, tmp_path, capsys, caplog):
     base, comp = (S.write(tmp_path, n, S.HEADER + SNV(1000)) for n in ("base.vcf", "comp.vcf"))
